@@ -7,6 +7,12 @@ pkg/chunk/disk_cache.go:1218-1231).  One "step" = one jfsx_seal_batch over
 the whole batch (keysetup + transform + finalize + result copy-back).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--blocks B] [--mode seal|open|crc]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full
+adds, after the timed region, the CPU baseline of the same work and the check
+of the results against the oracle.  --dump-outputs DIR writes what the last
+timed step returned as DIR/<name>.npy (dump_resident).
 
 For N > 1 it runs one rank per GPU: either launched by torch.distributed.run
 (the driver's form), or -- when WORLD_SIZE is unset -- it starts that launcher
@@ -101,6 +107,14 @@ def parse():
     ap.add_argument("--host-pool-gib", type=float, default=8.0,
                     help="host mode: pinned input pool per GPU (the output pool is the same size), NUMA-local to "
                          "the GPU; a step loops over it to make up the GPU's blocks")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline (cpu_baseline) and the "
+                         "check of the results against the oracle (--verify, full_check).  Without it a run sets up, "
+                         "warms up, times the steps and prints the line, with cpu_baseline and full_check null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="device-resident modes (seal, open, decrypt, crc): after the timed steps write what the "
+                         "last step returned to DIR/<name>.npy (float32 / float64): tags, CRC arrays and statuses of "
+                         "every block, and a fixed seeded sample of the output bytes")
     ap.add_argument("--dry-run", action="store_true",
                     help="test hook: the launcher, process group, shard layout, barrier and max-over-ranks timing "
                          "with no engine (no GPU); prints the JSON line with value null")
@@ -363,6 +377,12 @@ def main():
     global ORIG_AFFINITY
     ORIG_AFFINITY = os.sched_getaffinity(0)
     args = parse()
+    if not args.full:
+        # a plain run does only what its headline figure needs
+        args.no_cpu, args.verify = True, 0
+    if args.dump_outputs and (args.dry_run or args.mem != "device" or
+                              args.mode not in ("seal", "open", "decrypt", "crc")):
+        raise SystemExit("bench: --dump-outputs covers the device-resident seal / open / decrypt / crc modes")
     if args.engine == "mctx":
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise SystemExit("bench: --engine mctx is one process over --gpus GPUs; run it without the launcher")
@@ -591,6 +611,8 @@ def resident_bench(args, world, rank, local, dist):
         e.set_timing(False)
     el = max_over_ranks(dist, t1 - t0, local)
     ktimes = [e.kernel_time(reset=True) for e in engs]
+    if args.dump_outputs and rank == 0:
+        dump_resident(args, E, shards, loops)
 
     # checker only, after the timed region: every block against the oracle
     full, rsa = None, None
@@ -686,6 +708,64 @@ def resident_bench(args, world, rank, local, dist):
         engs[0].close()
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_BLOCKS = 512   # --dump-outputs: sampled blocks (seeded, with replacement), two chunks of each
+DUMP_CHUNK = 4096   # bytes per chunk
+
+
+def dump_resident(args, E, shards, loops):
+    """--dump-outputs DIR: what the last timed step handed back, as
+    DIR/<name>.npy, identical from run to run for the same arguments (the
+    inputs and the sample are seeded).  Rank 0 writes its own GPU's blocks
+    (--engine mctx: every GPU's), in shard order:
+      status            every block's descriptor status (float32)
+      tags              seal: the 16 tag bytes of every block (float32)
+      crc               seal with CRC full: every block's checksum() array as
+                        32-bit words, zero beyond the block's segments (float64)
+      ciphertext_sample / plaintext_sample
+                        seal / open, decrypt: DUMP_CHUNK bytes at a seeded
+                        offset and the last DUMP_CHUNK bytes of DUMP_BLOCKS
+                        seeded blocks of the output buffer (float32)
+    About 33 MB at the default size."""
+    import numpy as np
+    mode = args.mode
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    # the descriptor the last loop that ran each block used
+    last = [[None] * sh.nb for sh in shards]
+    for arr, _, parts in loops:
+        for sh, o, c in parts:
+            row = last[shards.index(sh)]
+            for i in range(c):
+                row[i] = arr[o + i]
+    recs = [r for row in last for r in row if r is not None]
+    out = {"status": np.array([r.status for r in recs], np.float32)}
+    if mode == "seal":
+        out["tags"] = np.frombuffer(b"".join(bytes(r.tag) for r in recs), np.uint8).reshape(-1, 16).astype(np.float32)
+        if args.crc == "full":
+            crcs = []
+            for sh in shards:
+                got = sh.crc.download(sh.nb * 4 * sh.nseg).reshape(sh.nb, 4 * sh.nseg)
+                cl = np.array([4 * max(1, -(-int(x) // E.SEG)) for x in sh.lens])
+                got = np.where(np.arange(4 * sh.nseg)[None, :] < cl[:, None], got, 0).astype(np.uint8)
+                crcs.append(got.view("<u4").astype(np.float64))
+            out["crc"] = np.concatenate(crcs)
+    if mode != "crc":
+        rng = np.random.default_rng(SEED)
+        where = [(sh, b) for sh in shards for b in range(sh.nb)]
+        picks = rng.integers(0, len(where), DUMP_BLOCKS)
+        frac = rng.random(DUMP_BLOCKS)
+        sample = np.zeros((2 * DUMP_BLOCKS, DUMP_CHUNK), np.float32)
+        for k in range(DUMP_BLOCKS):
+            sh, b = where[picks[k]]
+            buf = sh.dst if mode == "seal" else sh.src  # Open writes the plaintext back over the source
+            n = min(DUMP_CHUNK, sh.lens[b])
+            tail = sh.lens[b] - n
+            for j, o in enumerate((int(frac[k] * tail), tail)):
+                sample[2 * k + j, :n] = buf.download(n, offset=sh.offs[b] + o)
+        out["ciphertext_sample" if mode == "seal" else "plaintext_sample"] = sample
+    for name, a in out.items():
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
 
 
 def rsa_line(sh, rsae):

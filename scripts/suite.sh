@@ -3,7 +3,7 @@
 #
 # usage (on the GPU box, from the repo root; chain steps with &&):
 #   bash scripts/suite.sh <tag> tests                        pytest -m gpu (one process)
-#   bash scripts/suite.sh <tag> line <name> [bench args]     one bench.py JSON line -> bench_<name>.json
+#   bash scripts/suite.sh <tag> line <name> [bench args]     one bench.py --full JSON line -> bench_<name>.json
 #   bash scripts/suite.sh <tag> prof <name> [bench args]     rocprofv3 --kernel-trace --stats of that line
 #   bash scripts/suite.sh <tag> pmc <name> "<ctrs>" [args]   one rocprofv3 --pmc pass (--steps 1 --warmup 0)
 #   bash scripts/suite.sh <tag> smoke                        __graft_entry__.smoke()
@@ -32,8 +32,8 @@ smoke)
     exit $rc ;;
 line)
     name=$1; shift
-    echo "bench.py $*" > "$out/bench_$name.cmd"
-    timeout -k 10 ${TL} python3 -u bench.py "$@" > "$out/bench_$name.json" 2> "$out/bench_$name.err"
+    echo "bench.py --full $*" > "$out/bench_$name.cmd"
+    timeout -k 10 ${TL} python3 -u bench.py --full "$@" > "$out/bench_$name.json" 2> "$out/bench_$name.err"
     rc=$?
     if [ $rc -ne 0 ]; then echo "$name failed ($rc)"; tail -5 "$out/bench_$name.err"; exit $rc; fi
     echo "$name: $(tail -1 "$out/bench_$name.json" | cut -c1-200)" ;;

@@ -74,7 +74,7 @@ def test_bench_gpus_2_launches_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR",
                                                             "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run",
-                          "--blocks", "5", "--cpu-seconds", "0.2"], env=env, capture_output=True, text=True,
+                          "--full", "--blocks", "5", "--cpu-seconds", "0.2"], env=env, capture_output=True, text=True,
                          timeout=240)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
