@@ -15,6 +15,7 @@
  *   jfsx_data_decrypt    dataEncryptor.Decrypt (object format)      pkg/object/encrypt.go:196-216
  *   jfsx_checksum        checksum(data) []byte                      pkg/chunk/disk_cache.go:1218-1231
  *   jfsx_crc32c_segments the CRC loop of cacheFile.ReadAt           pkg/chunk/disk_cache.go:1315-1327
+ *   jfsx_file_checksum_batch getFileChecksum (MD5-of-MD5-of-CRC32C)  sdk/java/.../JuiceFileSystemImpl.java:1286-1343
  *   jfsx_cache_verify    cacheFile.ReadAt level logic + verify      pkg/chunk/disk_cache.go:1255-1329
  *   jfsx_object_crc32c   generateChecksum / checksumReader of the   pkg/object/checksum.go:31-82
  *   (+ JFSX_CRC_CT)      stored object, fused with Seal/Open        (s3.go:140-146,173-176)
@@ -339,6 +340,39 @@ int jfsx_agg_dev_batches(jfsx_agg *agg, int i, uint64_t *batches);
 /* checksum(data) on the GPU: out receives 4*max(1,ceil(len/32K)) bytes.
  * data and out are host memory. */
 int jfsx_checksum(jfsx_ctx *ctx, const void *data, uint64_t len, uint8_t *out);
+
+/* Hadoop's file checksum, MD5-of-MD5-of-CRC32C, what `hadoop fs -checksum` and
+ * distcp compare (getFileChecksum, sdk/java/src/main/java/io/juicefs/
+ * JuiceFileSystemImpl.java:1286-1343): a CRC32C per bytes_per_crc chunk (big
+ * endian), an MD5 over the chunk CRCs of every block_bytes of the file, and an
+ * MD5 over Hadoop's DataOutputBuffer of the block digests (its whole backing
+ * array: the 16 k digest bytes zero-padded to the smallest 32 * 2^j >= 16 k).
+ * A span with no chunk gives MD5(32 zero bytes) with crc32c = 0 and
+ * bytes_per_crc = crc_per_block = 0; otherwise crc32c = 1, bytes_per_crc as
+ * given and crc_per_block = len > block_bytes ? block_bytes / bytes_per_crc : 0. */
+typedef struct jfsx_fsum {
+    const void *data;        /* the span to hash: bytes [0, len) of the file   */
+    uint64_t len;            /* = jfsx_file_checksum_span(...)                 */
+    uint8_t md5[16];         /* out                                            */
+    uint32_t bytes_per_crc;  /* out: 512, or 0 when no chunk                   */
+    uint32_t crc32c;         /* out: 1 CRC32C, 0 CRC32 (the no-chunk case)     */
+    uint64_t crc_per_block;  /* out                                            */
+} jfsx_fsum;
+/* bytes of a file of file_size that getFileChecksum(f, length) hashes: it reads
+ * bytes_per_crc at a time while it has fewer than length, so a length that is
+ * no chunk multiple runs on to the chunk end (or EOF), except below one chunk */
+uint64_t jfsx_file_checksum_span(uint64_t file_size, uint64_t length, uint32_t bytes_per_crc);
+/* n files in one call: one chunk-CRC launch over all of them, one MD5 launch
+ * over all their blocks, one download of 16 bytes per block, the last MD5 on
+ * the host.  bytes_per_crc must be 512; block_bytes a non-zero multiple of it.
+ * JFSX_MEM_DEVICE: data 16-byte aligned.  JFSX_MEM_HOST: pageable or pinned
+ * memory at any alignment, staged through engine-owned pinned memory. */
+int jfsx_file_checksum_batch(jfsx_ctx *ctx, int n, jfsx_fsum *files,
+                             uint32_t bytes_per_crc, uint64_t block_bytes, int mem);
+/* host only, no device: the block and file MD5s over chunk CRCs already computed
+ * (big-endian words), e.g. by the fused Seal/Open CRC_GEN of a <= 512 B block */
+int jfsx_file_checksum_fold(const uint8_t *chunk_crcs, uint64_t nchunks, uint64_t span_len,
+                            uint32_t bytes_per_crc, uint64_t block_bytes, jfsx_fsum *out);
 
 /* cacheFile.ReadAt verify (disk_cache.go:1255-1329) over an in-memory cache
  * file image: file = data(length) ‖ BE32 CRCs, level 0 none / 1 full /

@@ -11,7 +11,12 @@ The bytes are hashed on the GPU as 32 KiB segment CRCs (jfsx_crc32c_segments)
 and folded into the whole-object value on the host (jfsx_crc32c_combine);
 Encrypted stores get it fused into the Seal/Open pass instead (JFSX_CRC_CT,
 encrypt.DataEncryptor.EncryptBatch(checksums=True)).
+
+getFileChecksum mirrors the Hadoop SDK's file checksum (`hadoop fs -checksum`,
+distcp): sdk/java/src/main/java/io/juicefs/JuiceFileSystemImpl.java:1286-1343,
+MD5-of-MD5-of-CRC32C through jfsx_file_checksum_batch.
 """
+import collections
 import re
 
 import numpy as np
@@ -43,6 +48,26 @@ def crc32c(data, eng=None):
         lj = min(_SEG, d.size - j * _SEG)
         crc = eng.crc32c_combine(crc, int.from_bytes(segs[4 * j:4 * j + 4], "big"), lj)
     return crc
+
+
+FileChecksum = collections.namedtuple("FileChecksum", "crc_type bytesPerCRC crcPerBlock md5hex")
+FileChecksum.__doc__ = """What MD5MD5CRC32FileChecksum carries: the CRC type ("CRC32C", or "CRC32" --
+MD5MD5CRC32GzipFileChecksum -- when nothing was hashed), bytesPerCRC,
+crcPerBlock and the MD5 as hex."""
+
+
+def getFileChecksum(data, length=None, blocksize=128 << 20, bytesPerCrc=512, eng=None):
+    """JuiceFileSystemImpl.getFileChecksum(f, length) of a file whose bytes are
+    `data`: CRC32C per bytesPerCrc chunk, MD5 per blocksize of the file, MD5
+    over the block digests.  length=None is Long.MAX_VALUE (the whole file);
+    a length that is no chunk multiple runs on to the chunk end or EOF, as the
+    reference's read loop does (jfsx_file_checksum_span)."""
+    eng = eng or default_engine()
+    d = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).ravel()
+    d = np.ascontiguousarray(d)
+    span = E.file_checksum_span(d.size, (1 << 63) - 1 if length is None else length, bytesPerCrc)
+    c32c, bpc, cpb, md5 = eng.file_checksum_batch([(d, span)], blocksize, bytesPerCrc, mem=E.MEM_HOST)[0]
+    return FileChecksum("CRC32C" if c32c else "CRC32", bpc, cpb, md5.hex())
 
 
 def generateChecksum(data, eng=None):

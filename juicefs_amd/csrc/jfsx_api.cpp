@@ -27,6 +27,7 @@
 
 #define JFSX_HD static inline
 #include "jfsx_rsa.h"
+#include "jfsx_md5.h"
 
 using namespace jfsx;
 
@@ -283,6 +284,26 @@ void make_crc_tables(std::vector<uint32_t> &crc, std::vector<uint32_t> &crcx) {
     for (int l = 0; l < 64; l++) crcx[128 + l] = xpow8(64 * (63 - l));
 }
 
+// crc_chunks_k's chunk-end multiplies (jfsx_crc.hip): the lane CRC of the
+// 64-byte piece at position pos of a 512-byte chunk times x^(8 * 64 * (7 - pos)),
+// as 8 nibble tables per pos: m[((t * 2 + hi) * 16 + nib) * 8 + pos] is the
+// product for nibble hi of byte t.  *k512 = x^(8 * 512) * 0xffffffff, the
+// init/xorout term of a whole chunk.
+void make_crc_chunk_mul(std::vector<uint32_t> &m, uint32_t *k512) {
+    uint32_t x64 = 0x00800000u;  // x^8, squared six times: x^(8 * 64)
+    for (int k = 0; k < 6; k++) x64 = crc_mulmod_h(x64, x64);
+    uint32_t xp[8];
+    xp[7] = 0x80000000u;  // x^0
+    for (int pos = 6; pos >= 0; pos--) xp[pos] = crc_mulmod_h(xp[pos + 1], x64);
+    m.assign(4 * 2 * 16 * 8, 0);
+    for (uint32_t t = 0; t < 4; t++)
+        for (uint32_t hi = 0; hi < 2; hi++)
+            for (uint32_t nib = 0; nib < 16; nib++)
+                for (uint32_t pos = 0; pos < 8; pos++)
+                    m[((t * 2 + hi) * 16 + nib) * 8 + pos] = crc_mulmod_h(xp[pos], (nib << (4 * hi)) << (8 * t));
+    *k512 = crc_mulmod_h(crc_mulmod_h(xp[0], x64), 0xffffffffu);
+}
+
 inline uint64_t nseg_of(uint64_t len) { return len ? (len + kSeg - 1) / kSeg : 1; }
 
 struct Plan {
@@ -366,7 +387,9 @@ struct jfsx_ctx {
     hipStream_t s_out = nullptr;   // host-ingest D2H
     hipStream_t s_ks = nullptr;    // host pipeline: descriptor pull + keysetup of the next group
     std::mutex mu;                 // enqueue order on the streams; the synchronous paths' workspace
-    uint32_t *d_tab = nullptr;  // aes | crc | crcx
+    uint32_t *d_tab = nullptr;  // aes | crc | crcx | crc_chunk_mul
+    const uint32_t *d_chunk_mul = nullptr;  // crc_chunks_k's chunk-end multiplies (make_crc_chunk_mul)
+    uint32_t k512 = 0;
     DevTables tabs{};
     Workspace ws[kRing];
     hipEvent_t ev_k0[kRing] = {}, ev_k1[kRing] = {};  // main-kernel timing of the synchronous paths
@@ -1785,7 +1808,9 @@ int jfsx_ctx_open(int device, uint32_t flags, jfsx_ctx **out) {
     std::vector<uint32_t> aes, crc, crcx;
     make_aes_table(aes);
     make_crc_tables(crc, crcx);
-    const size_t nbytes = 4 * (aes.size() + crc.size() + crcx.size());
+    std::vector<uint32_t> cmul;
+    make_crc_chunk_mul(cmul, &c->k512);
+    const size_t nbytes = 4 * (aes.size() + crc.size() + crcx.size() + cmul.size());
     if (hipMalloc((void **)&c->d_tab, nbytes) != hipSuccess) {
         c->d_tab = nullptr;
         jfsx_ctx_close(c);  // the streams made above
@@ -1795,6 +1820,7 @@ int jfsx_ctx_open(int device, uint32_t flags, jfsx_ctx **out) {
     all.insert(all.end(), aes.begin(), aes.end());
     all.insert(all.end(), crc.begin(), crc.end());
     all.insert(all.end(), crcx.begin(), crcx.end());
+    all.insert(all.end(), cmul.begin(), cmul.end());
     if (hipMemcpy(c->d_tab, all.data(), nbytes, hipMemcpyHostToDevice) != hipSuccess) {
         jfsx_ctx_close(c);
         return JFSX_EIO;
@@ -1802,6 +1828,7 @@ int jfsx_ctx_open(int device, uint32_t flags, jfsx_ctx **out) {
     c->tabs.aes = c->d_tab;
     c->tabs.crc = c->d_tab + aes.size();
     c->tabs.crcx = c->d_tab + aes.size() + crc.size();
+    c->d_chunk_mul = c->tabs.crcx + crcx.size();
     for (int k = 0; k < kRing; k++) {
         if (hipEventCreate(&c->ev_k0[k]) != hipSuccess || hipEventCreate(&c->ev_k1[k]) != hipSuccess) {
             jfsx_ctx_close(c);
@@ -2225,6 +2252,225 @@ int jfsx_checksum(jfsx_ctx *c, const void *data, uint64_t len, uint8_t *out) {
         return 0;
     }
     return jfsx_crc32c_segments(c, 1, &r, JFSX_CRC_GEN, JFSX_MEM_HOST);
+}
+
+// ---------------------------------------------------------------------------
+// Hadoop file checksum, MD5-of-MD5-of-CRC32C (getFileChecksum,
+// sdk/java/src/main/java/io/juicefs/JuiceFileSystemImpl.java:1286-1343)
+// ---------------------------------------------------------------------------
+namespace {
+constexpr uint32_t kFsumBpc = 512;                // bytesPerCRC: Hadoop's default, the only value the reference pins
+constexpr size_t kFsumStage = (size_t)16 << 20;  // host data: bytes staged per round
+
+// The file MD5 over the k block digests: Hadoop hashes DataOutputBuffer
+// .getData(), the whole backing array (32 bytes at first, grown to
+// max(2 * cap, needed) by the 16-byte appends), so the 16 k digest bytes
+// zero-padded to the smallest 32 * 2^j that holds them.
+void fsum_finish(const uint8_t *digests, uint64_t k, uint64_t span_len, uint64_t block_bytes, jfsx_fsum *f) {
+    uint64_t cap = 32;
+    while (cap < 16 * k) cap *= 2;
+    static const uint8_t zeros[256] = {0};
+    jfsx_md5::Ctx m;
+    jfsx_md5::init(&m);
+    if (k) jfsx_md5::update(&m, digests, 16 * k);
+    for (uint64_t pad = cap - 16 * k; pad;) {
+        const uint64_t t = std::min<uint64_t>(pad, sizeof(zeros));
+        jfsx_md5::update(&m, zeros, t);
+        pad -= t;
+    }
+    jfsx_md5::final(&m, f->md5);
+    f->bytes_per_crc = k ? kFsumBpc : 0;
+    f->crc32c = k ? 1 : 0;
+    f->crc_per_block = k && span_len > block_bytes ? block_bytes / kFsumBpc : 0;
+}
+
+struct FsumPiece {
+    int file;
+    uint64_t off, len;  // of the file; off % 4096 == 0
+    size_t soff;        // host data: offset in the staging buffers
+};
+
+// The batch under c->mu.  The data is cut into rounds of pieces: device
+// memory is one round with every file a piece; host memory goes through the
+// pinned bounce buffer and the device staging buffer in rounds of up to
+// kFsumStage bytes, pieces of whole 4 KiB spans (but a file's last), which the
+// chunk-CRC kernel hashes independently into the files' chunk-CRC arrays.
+int run_file_checksum(jfsx_ctx *c, int n, jfsx_fsum *f, uint64_t block_bytes, bool device, char *bounce,
+                      size_t stage_cap) {
+    const uint64_t per = block_bytes / kFsumBpc;
+    std::vector<uint64_t> w0(n + 1, 0), b0(n + 1, 0);  // first chunk-CRC word / DFS block of file i
+    for (int i = 0; i < n; i++) {
+        const uint64_t nch = (f[i].len + kFsumBpc - 1) / kFsumBpc;
+        w0[i + 1] = w0[i] + nch;
+        b0[i + 1] = b0[i] + (nch + per - 1) / per;
+    }
+    const uint64_t W = w0[n], B = b0[n];
+    if (B > 0xffffffffull) return JFSX_EINVAL;
+    if (W == 0) {
+        for (int i = 0; i < n; i++) fsum_finish(nullptr, 0, 0, block_bytes, &f[i]);
+        return 0;
+    }
+    std::vector<std::vector<FsumPiece>> rounds(1);
+    if (device) {
+        for (int i = 0; i < n; i++)
+            if (f[i].len) rounds[0].push_back(FsumPiece{i, 0, f[i].len, 0});
+    } else {
+        size_t used = 0;
+        for (int i = 0; i < n; i++)
+            for (uint64_t off = 0; off < f[i].len;) {
+                const uint64_t room = (stage_cap - used) & ~(uint64_t)4095;
+                const uint64_t take = std::min<uint64_t>(f[i].len - off, room);
+                if (!take) {
+                    rounds.emplace_back();
+                    used = 0;
+                    continue;
+                }
+                rounds.back().push_back(FsumPiece{i, off, take, used});
+                used += (take + 4095) & ~(size_t)4095;
+                off += take;
+            }
+    }
+    // tasks of every round, cut as enqueue_crc cuts them
+    std::vector<std::vector<Task>> rtasks(rounds.size());
+    size_t max_tasks = 1, max_pieces = 1;
+    for (size_t r = 0; r < rounds.size(); r++) {
+        uint64_t total = 0;
+        for (const FsumPiece &p : rounds[r]) total += p.len;
+        const uint64_t tb = crc_task_bytes(total);
+        for (size_t k = 0; k < rounds[r].size(); k++)
+            for (uint64_t c0 = 0; c0 < rounds[r][k].len; c0 += tb)
+                rtasks[r].push_back(Task{(uint32_t)k, 0, c0, std::min(c0 + tb, rounds[r][k].len)});
+        max_tasks = std::max(max_tasks, rtasks[r].size());
+        max_pieces = std::max(max_pieces, rounds[r].size());
+    }
+    Workspace &w = c->ws[0];
+    size_t off = 0;
+    const size_t o_blk = off; off = align256(off + sizeof(BlkDev) * max_pieces);
+    const size_t o_task = off; off = align256(off + sizeof(Task) * max_tasks);
+    const size_t o_job = off; off = align256(off + sizeof(Md5Job) * B);
+    const size_t h_bytes = off;
+    const size_t o_dig = off; off = align256(off + 16 * B);
+    const size_t o_words = off; off = align256(off + 4 * W);
+    int rc;
+    if ((rc = ensure_dev(c, &w.d, &w.dcap, off))) return rc;
+    if ((rc = ensure_host(&w.h, &w.hcap, h_bytes + 16 * B))) return rc;
+    if (!device && (rc = ensure_dev(c, &w.stage, &w.scap, stage_cap))) return rc;
+    char *h = w.h, *d = w.d;
+    uint32_t *words = (uint32_t *)(d + o_words);
+    Md5Job *jobs = (Md5Job *)(h + o_job);
+    for (int i = 0; i < n; i++) {
+        const uint64_t nch = w0[i + 1] - w0[i];
+        for (uint64_t b = 0; b < b0[i + 1] - b0[i]; b++)
+            jobs[b0[i] + b] = Md5Job{w0[i] + b * per, std::min(per, nch - b * per)};
+    }
+    const hipStream_t s = c->stream;
+    launch_begin();
+    HIP_OK(hipMemcpyAsync(d + o_job, h + o_job, sizeof(Md5Job) * B, hipMemcpyHostToDevice, s));
+    bool timed = false;
+    // wait for the stream; then the CRC kernel's time of the round just run
+    auto settle = [&]() -> int {
+        HIP_OK(hipStreamSynchronize(s));
+        if (timed) {
+            float ms = 0;
+            timed = false;
+            HIP_OK(hipEventElapsedTime(&ms, c->ev_k0[0], c->ev_k1[0]));
+            add_kernel_ms(c, ms);
+        }
+        return 0;
+    };
+    for (size_t r = 0; r < rounds.size(); r++) {
+        const std::vector<FsumPiece> &ps = rounds[r];
+        if (ps.empty()) continue;
+        BlkDev *hb = (BlkDev *)(h + o_blk);
+        size_t extent = 0;
+        for (size_t k = 0; k < ps.size(); k++) {
+            const FsumPiece &p = ps[k];
+            memset(&hb[k], 0, sizeof(BlkDev));
+            hb[k].len = p.len;
+            hb[k].crc_calc = words + w0[p.file] + p.off / kFsumBpc;
+            if (device) {
+                hb[k].src = (const uint8_t *)f[p.file].data + p.off;
+            } else {
+                memcpy(bounce + p.soff, (const char *)f[p.file].data + p.off, p.len);
+                hb[k].src = (const uint8_t *)w.stage + p.soff;
+                extent = p.soff + p.len;
+            }
+        }
+        memcpy(h + o_task, rtasks[r].data(), sizeof(Task) * rtasks[r].size());
+        HIP_OK(hipMemcpyAsync(d, h, o_job, hipMemcpyHostToDevice, s));
+        if (extent) {
+            HIP_OK(hipMemcpyAsync(w.stage, bounce, extent, hipMemcpyHostToDevice, s));
+            bounce_count(c, extent, 0);
+        }
+        if (c->timing) HIP_OK(hipEventRecord(c->ev_k0[0], s));
+        launch_crc_chunks(s, (int)rtasks[r].size(), (const Task *)(d + o_task), (const BlkDev *)(d + o_blk), c->tabs,
+                          c->d_chunk_mul, c->k512);
+        if (c->timing) HIP_OK(hipEventRecord(c->ev_k1[0], s));
+        timed = c->timing;
+        HIP_OK(hipGetLastError());
+        // the descriptors' mirror and the staging buffers are rewritten by the next round
+        if (r + 1 < rounds.size() && (rc = settle())) return rc;
+    }
+    launch_md5_blocks(s, (uint32_t)B, (const Md5Job *)(d + o_job), words, (uint32_t *)(d + o_dig));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(h + h_bytes, d + o_dig, 16 * B, hipMemcpyDeviceToHost, s));
+    if ((rc = settle())) return rc;
+    for (int i = 0; i < n; i++)
+        fsum_finish((const uint8_t *)h + h_bytes + 16 * b0[i], b0[i + 1] - b0[i], f[i].len, block_bytes, &f[i]);
+    return 0;
+}
+}  // namespace
+
+uint64_t jfsx_file_checksum_span(uint64_t file_size, uint64_t length, uint32_t bytes_per_crc) {
+    if (!bytes_per_crc) return 0;
+    if (length < bytes_per_crc) return std::min(file_size, length);
+    const uint64_t chunks = length / bytes_per_crc + (length % bytes_per_crc ? 1 : 0);
+    if (chunks > UINT64_MAX / bytes_per_crc) return file_size;
+    return std::min(file_size, chunks * bytes_per_crc);
+}
+
+int jfsx_file_checksum_batch(jfsx_ctx *c, int n, jfsx_fsum *files, uint32_t bytes_per_crc, uint64_t block_bytes,
+                             int mem) {
+    if (!c || n < 0 || (n > 0 && !files)) return JFSX_EINVAL;
+    if (mem != JFSX_MEM_HOST && mem != JFSX_MEM_DEVICE) return JFSX_EINVAL;
+    if (bytes_per_crc != kFsumBpc || !block_bytes || block_bytes % kFsumBpc) return JFSX_EINVAL;
+    const bool device = mem == JFSX_MEM_DEVICE;
+    uint64_t total = 0, staged = 0;
+    for (int i = 0; i < n; i++) {
+        if (files[i].len && (!files[i].data || (device && !aligned16(files[i].data)))) return JFSX_EINVAL;
+        total += files[i].len;
+        staged += (files[i].len + 4095) & ~(uint64_t)4095;
+    }
+    if (n == 0) return 0;
+    std::lock_guard<std::mutex> g(c->mu);
+    CtxScope es_(c);
+    HIP_OK(hipSetDevice(c->device));
+    char *bounce = nullptr;
+    size_t bcap = 0;
+    const size_t stage_cap = (size_t)std::min<uint64_t>(kFsumStage, std::max<uint64_t>(staged, 4096));
+    if (!device && total && !(bounce = bounce_get(c, stage_cap, &bcap))) return JFSX_ENOMEM;
+    const int rc = run_file_checksum(c, n, files, block_bytes, device, bounce, stage_cap);
+    if (rc) (void)hipStreamSynchronize(c->stream);  // nothing in flight reads the buffers once the call returns
+    if (bounce) bounce_put(c, bounce, bcap);
+    if (rc == 0) {
+        std::lock_guard<std::mutex> sg(c->stat_mu);
+        c->met.crc_batches++;
+        c->met.crc_ranges += n;
+        c->met.crc_bytes += total;
+    }
+    return rc;
+}
+
+int jfsx_file_checksum_fold(const uint8_t *chunk_crcs, uint64_t nchunks, uint64_t span_len, uint32_t bytes_per_crc,
+                            uint64_t block_bytes, jfsx_fsum *out) {
+    if (!out || bytes_per_crc != kFsumBpc || !block_bytes || block_bytes % kFsumBpc) return JFSX_EINVAL;
+    if ((nchunks && !chunk_crcs) || nchunks != span_len / kFsumBpc + (span_len % kFsumBpc ? 1 : 0)) return JFSX_EINVAL;
+    const uint64_t per = block_bytes / kFsumBpc, k = (nchunks + per - 1) / per;
+    std::vector<uint8_t> digests(16 * k);
+    for (uint64_t b = 0; b < k; b++)
+        jfsx_md5::digest(chunk_crcs + 4 * per * b, 4 * std::min(per, nchunks - per * b), digests.data() + 16 * b);
+    fsum_finish(digests.data(), k, span_len, block_bytes, out);
+    return 0;
 }
 
 int jfsx_cache_verify(jfsx_ctx *c, const void *file, uint64_t file_size, uint64_t length, int level, uint64_t off,

@@ -1,5 +1,6 @@
-// jfsx_crc.hip -- CRC32C per 32 KiB segment over ranges (gfx950), and the
-// synthetic-input generator.
+// jfsx_crc.hip -- CRC32C per 32 KiB segment over ranges (gfx950), the Hadoop
+// file checksum's kernels (CRC32C per 512-byte chunk, MD5 per DFS block), and
+// the synthetic-input generator.
 //
 // crc32c_segments replaces the CRC loops of checksum() (pkg/chunk/disk_cache.go:
 // 1218-1231) and of cacheFile.ReadAt (disk_cache.go:1315-1327) for cache hits,
@@ -8,6 +9,9 @@
 // LDS; lane CRCs are shifted to the segment end (GF(2) multiply by x^(8d) mod P)
 // and XOR-reduced across the wave.
 #include "jfsx_dev.h"
+
+#define JFSX_MD5_HD __host__ __device__ __forceinline__
+#include "jfsx_md5.h"
 
 namespace jfsx {
 
@@ -373,6 +377,221 @@ __global__ __launch_bounds__(kCrcWaves * 64) __attribute__((amdgpu_waves_per_eu(
                 *reinterpret_cast<uint32_t *>(blk.crc + 4 * si) = __builtin_bswap32(crc);
         }
     }
+}
+
+// ---------------------------------------------------------------------------
+// Hadoop file checksum (MD5-of-MD5-of-CRC32C), CRC phase: one CRC32C per
+// 512-byte chunk of a file (getFileChecksum, sdk/java/.../JuiceFileSystemImpl
+// .java:1297-1342; bytesPerCRC = 512), written as one big-endian word per
+// chunk at index offset / 512 of the file's chunk-CRC array (blk.crc_calc).
+//
+// Same machine as crc_segments_k's default path: byte tables U12..U15 in LDS
+// (one replica per bank), quad-transposed coalesced non-temporal loads, two
+// interleaved slice-by-4 chains, a wave takes a 32 KiB run of 8 spans of 4 KiB
+// and a lane a 64-byte piece of each span.  The piece with span index
+// ci = crc_chunk_idx(lane) is position pos = ci & 7 of chunk ci >> 3, so the
+// lane CRC has to move 64 * (7 - pos) bytes to the chunk end: a multiply by
+// x^(8 * 64 * (7 - pos)) (crcx[128 + 56 + pos]).  pos is fixed per lane, and
+// lanes l and l + 32 share both their LDS bank and their pos, so the multiply
+// is a linear map looked up in region 2, where crc_segments_k keeps its
+// 4096-byte shift: the nibble tables of bank b hold the map of pos(b)
+// (crc_chunk_mul, 1024 words built by the host).  That is 8 conflict-free
+// lookups per span, what the span shift costs crc_segments_k, against about
+// 190 VALU operations for a crc_mulmod -- more than the 16 table steps of the
+// span itself.  The 8 lanes of a chunk are then XORed together: with
+// JFSX_CRC_XPOSE they are the lanes 4 apart inside a 32-lane half (lane bits
+// 2..4), reduced by two DPP row rotates (row_ror:4, row_ror:8: all lanes of a
+// 16-lane row with the same lane & 3) and one ds_swizzle (xor 16); no LDS
+// memory and no barrier.  K512 = x^(8 * 512) * 0xffffffff, the init/xorout
+// term of a 512-byte message, comes from the host.
+// A run shorter than 32 KiB (the end of a file) goes span by span through
+// crc_chunks_span_g: guarded loads (load_piece), the last 1..3 bytes of the
+// file through the global byte table, and for the file's short last chunk a
+// crc_mulmod by the distance to its end.
+__device__ __forceinline__ uint32_t chunk_xor8(uint32_t v) {
+#if JFSX_CRC_XPOSE
+    v ^= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x124, 0xF, 0xF, true);  // row_ror:4
+    v ^= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x128, 0xF, 0xF, true);  // row_ror:8
+    v ^= (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401F);              // lane ^ 16
+#else
+    v ^= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);  // lane ^ 1
+    v ^= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true);  // lane ^ 2
+    v ^= (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x101F);             // lane ^ 4
+#endif
+    return v;
+}
+
+#if JFSX_CRC_BYTE
+// one span [s0, min(s0 + 4096, end)) of a file, every load guarded
+__device__ __noinline__ void crc_chunks_span_g(const char *lds, uint32_t lb, const uint32_t *__restrict__ T,
+                                               const uint32_t *__restrict__ crcx, const uint8_t *src, uint64_t s0,
+                                               uint64_t end, uint32_t *__restrict__ out, uint32_t lane,
+                                               uint32_t K512) {
+    const uint32_t ci = crc_chunk_idx(lane);
+    const uint64_t o = s0 + 64 * ci;
+    const uint32_t n = o >= end ? 0u : (end - o < 64 ? (uint32_t)(end - o) : 64u);
+    uint32_t pw[16];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const uint4 p = load_piece(src, o + 16 * j, end);
+        pw[4 * j] = p.x, pw[4 * j + 1] = p.y, pw[4 * j + 2] = p.z, pw[4 * j + 3] = p.w;
+    }
+    uint32_t c = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < 16; w++) {
+        if (4 * w + 4 <= n) {
+            c = crc_step4(lds, lb, c ^ pw[w]);
+        } else if (4 * w < n) {
+            for (uint32_t i = 0; i < n - 4 * w; i++)
+                c = T[15 * 256 + ((c ^ (pw[w] >> (8 * i))) & 0xffu)] ^ (c >> 8);
+        }
+    }
+    const uint64_t cs = s0 + 512 * (uint64_t)(ci >> 3);  // the chunk's first byte
+    uint32_t v = 0, K = K512;
+    if (cs + 512 <= end) {
+        v = crc_shift4096(lds, lb, c);  // a whole chunk: the lane's map (crc_chunk_mul)
+    } else if (n) {
+        // the file's short last chunk [cs, end): the piece ends d bytes before it does
+        const uint64_t d = end - (o + n);
+        v = d ? crc_mulmod(crc_xpow8(d, crcx + 64), c) : c;
+        K = crc_mulmod(crc_xpow8(end - cs, crcx + 64), 0xffffffffu);
+    }
+    const uint32_t raw = chunk_xor8(v);
+    if ((ci & 7u) == 0 && cs < end) out[cs >> 9] = __builtin_bswap32(~(K ^ raw));
+}
+
+__global__ __launch_bounds__(kCrcWaves * 64) __attribute__((amdgpu_waves_per_eu(JFSX_CRC_WPE))) void crc_chunks_k(
+    const Task *__restrict__ tasks, const BlkDev *__restrict__ blks, DevTables tab,
+    const uint32_t *__restrict__ crc_chunk_mul, uint32_t K512) {
+    __shared__ __attribute__((aligned(16))) char lds[kCrcLds];
+    const Task task = tasks[blockIdx.x];
+    const BlkDev blk = blks[task.blk];
+    const uint32_t tid = threadIdx.x;
+    // stage: byte tables U12..U15, i = (table t, entry e, replica quad rq)
+    for (uint32_t i = tid; i < 4 * 256 * 8; i += kCrcWaves * 64) {
+        const uint32_t rq = i & 7, e = (i >> 3) & 255, t = i >> 11;
+        const uint32_t v = tab.crc[(12 + t) * 256 + e];
+        *reinterpret_cast<uint4 *>(lds + (t >> 1) * 0x10000u + e * 256 + (t & 1) * 128 + 16 * rq) =
+            make_uint4(v, v, v, v);
+    }
+    // region 2, the chunk-end multiply as nibble tables: i = (table t, hi,
+    // nibble, bank); bank b holds the map of the pos its two lanes have
+    for (uint32_t i = tid; i < 4 * 2 * 16 * 32; i += kCrcWaves * 64) {
+        const uint32_t bank = i & 31, nib = (i >> 5) & 15, hi = (i >> 9) & 1, t = i >> 10;
+        const uint32_t pos = crc_chunk_idx(bank) & 7u;
+        *reinterpret_cast<uint32_t *>(lds + 0x20000u + t * 4096 + nib * 256 + hi * 128 + 4 * bank) =
+            crc_chunk_mul[((t * 2 + hi) * 16 + nib) * 8 + pos];
+    }
+    __syncthreads();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const uint32_t lb = ((lane & 31) << 2) | 0x10000u | 0x2000000u;
+    const uint8_t *src = blk.src;
+    uint32_t *__restrict__ out = blk.crc_calc;
+    const uint32_t ci = crc_chunk_idx(lane);
+    for (uint64_t seg0 = task.c0 + (uint64_t)wave * kSeg; seg0 < task.c1; seg0 += (uint64_t)kCrcWaves * kSeg) {
+        if (seg0 + kSeg > task.c1) {
+            for (uint64_t s0 = seg0; s0 < task.c1; s0 += 4096)
+                crc_chunks_span_g(lds, lb, tab.crc, tab.crcx, src, s0, task.c1, out, lane, K512);
+            continue;
+        }
+        // a whole 32 KiB run: the loop of crc_segments_k's default path, with
+        // the span shift replaced by the chunk combine
+        constexpr int CH = JFSX_CRC_CHAINS;
+        uint4 buf[CH][4];
+#pragma unroll
+        for (int k = 0; k < CH; k++)
+#pragma unroll
+            for (int j = 0; j < 4; j++) buf[k][j] = crc_chunk_ld(src + seg0, lane, k, j);
+#pragma unroll
+        for (int r = 0; r < 8; r += CH) {
+            if (JFSX_CRC_XPOSE) {
+#pragma unroll
+                for (int k = 0; k < CH; k++) quad_xpose(buf[k], lane);
+            }
+            uint32_t x[CH];
+#pragma unroll
+            for (int k = 0; k < CH; k++) x[k] = buf[k][0].x;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+#pragma unroll
+                for (int k = 0; k < CH; k++) x[k] = crc_step4x(lds, lb, x[k], buf[k][j].y);
+#pragma unroll
+                for (int k = 0; k < CH; k++) x[k] = crc_step4x(lds, lb, x[k], buf[k][j].z);
+                if (j < 3) {
+#pragma unroll
+                    for (int k = 0; k < CH; k++) x[k] = crc_step4x(lds, lb, x[k], buf[k][j].w);
+#pragma unroll
+                    for (int k = 0; k < CH; k++) x[k] = crc_step4x(lds, lb, x[k], buf[k][j + 1].x);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < CH; k++) x[k] = crc_step4x(lds, lb, x[k], buf[k][j].w);
+                }
+                if (r + CH < 8 && j > 0) {
+#pragma unroll
+                    for (int k = 0; k < CH; k++) buf[k][j - 1] = crc_chunk_ld(src + seg0, lane, r + CH + k, j - 1);
+                }
+            }
+            if (r + CH < 8) {
+#pragma unroll
+                for (int k = 0; k < CH; k++) buf[k][3] = crc_chunk_ld(src + seg0, lane, r + CH + k, 3);
+            }
+#pragma unroll
+            for (int k = 0; k < CH; k++) {
+                // x[k] = crc_raw(0, the lane's piece of span r + k), still to
+                // go through its last table step
+                const uint32_t raw = chunk_xor8(crc_shift4096(lds, lb, crc_step4(lds, lb, x[k])));
+                if ((ci & 7u) == 0) out[((seg0 + 4096 * (r + k)) >> 9) + (ci >> 3)] = __builtin_bswap32(~(K512 ^ raw));
+            }
+        }
+    }
+}
+#endif
+
+// Hadoop file checksum, block phase: lane b hashes the nw[b] chunk-CRC words
+// of DFS block b (4 * min(crcPerBlock, chunks left) bytes at words + w0[b];
+// the words are the big-endian CRC bytes as stored, so the little-endian load
+// already is MD5's message word) and writes the 16-byte digest.  Serial per
+// block by nature, about 16384 compressions for a 128 MiB block; the next
+// 64 bytes are loaded while the current ones are hashed.
+__global__ __launch_bounds__(64) void md5_blocks_k(const Md5Job *__restrict__ jobs, uint32_t njobs,
+                                                  const uint32_t *__restrict__ words,
+                                                  uint32_t *__restrict__ digests) {
+    const uint32_t b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= njobs) return;
+    const Md5Job job = jobs[b];
+    const uint32_t *p = words + job.w0;
+    const uint64_t nfull = job.nw / 16;
+    uint32_t st[4], cur[16], nxt[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) nxt[i] = 0;
+    jfsx_md5::iv(st);
+    if (nfull) {
+#pragma unroll
+        for (int i = 0; i < 16; i++) cur[i] = p[i];
+    }
+    for (uint64_t k = 0; k < nfull; k++) {
+        if (k + 1 < nfull) {
+#pragma unroll
+            for (int i = 0; i < 16; i++) nxt[i] = p[16 * (k + 1) + i];
+        }
+        jfsx_md5::compress(st, cur);
+#pragma unroll
+        for (int i = 0; i < 16; i++) cur[i] = nxt[i];
+    }
+    jfsx_md5::finish_words(st, job.nw, [&](uint64_t i) { return p[i]; });
+#pragma unroll
+    for (int i = 0; i < 4; i++) digests[4 * b + i] = st[i];
+}
+
+void launch_crc_chunks(hipStream_t s, int ntasks, const Task *tasks, const BlkDev *blks, DevTables t,
+                       const uint32_t *crc_chunk_mul, uint32_t K512) {
+    if (ntasks > 0)
+        hipLaunchKernelGGL(crc_chunks_k, dim3(ntasks), dim3(kCrcWaves * 64), 0, s, tasks, blks, t, crc_chunk_mul, K512);
+}
+
+void launch_md5_blocks(hipStream_t s, uint32_t njobs, const Md5Job *jobs, const uint32_t *words, uint32_t *digests) {
+    if (njobs > 0)
+        hipLaunchKernelGGL(md5_blocks_k, dim3((njobs + 63) / 64), dim3(64), 0, s, jobs, njobs, words, digests);
 }
 
 // zero-length ranges/blocks still produce one zero CRC (Go's checksum(): 4 bytes)

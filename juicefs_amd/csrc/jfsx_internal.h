@@ -314,6 +314,17 @@ void launch_cp_finalize(hipStream_t s, int n, bool open, int crc_mode, const Blk
                         const uint32_t *partial, const uint32_t *pexp, BlkOut *out);
 void launch_crc_segments(hipStream_t s, int ntasks, const Task *tasks, const BlkDev *blks, DevTables t);
 void launch_crc_finalize(hipStream_t s, int n, int crc_mode, const BlkDev *blks, BlkOut *out);
+// Hadoop file checksum (jfsx_crc.hip): CRC32C per 512-byte chunk of the tasks'
+// ranges into blk.crc_calc[offset / 512] (big-endian words; c0 % 4096 == 0),
+// then one MD5 per DFS block over words[w0, w0 + nw) into digests[4 * job].
+// crc_chunk_mul: 1024 words, the chunk-end multiplies as nibble tables
+// (make_crc_chunk_mul, jfsx_api.cpp); K512 = x^(8 * 512) * 0xffffffff
+struct Md5Job {
+    uint64_t w0, nw;
+};
+void launch_crc_chunks(hipStream_t s, int ntasks, const Task *tasks, const BlkDev *blks, DevTables t,
+                       const uint32_t *crc_chunk_mul, uint32_t K512);
+void launch_md5_blocks(hipStream_t s, uint32_t njobs, const Md5Job *jobs, const uint32_t *words, uint32_t *digests);
 void launch_gen_synthetic(hipStream_t s, uint8_t *dst, uint64_t len, uint64_t seed, uint64_t block);
 void launch_pull(hipStream_t s, void *dst, const void *src, size_t bytes);
 void launch_gen_synthetic_batch(hipStream_t s, uint8_t *dst, uint64_t stride, int n, const uint64_t *lens,

@@ -48,6 +48,7 @@ EXPORTS = [
     "jfsx_device_numa_node", "jfsx_alloc_pinned_node", "jfsx_host_numa_node",
     "jfsx_agg_data_encrypt", "jfsx_agg_data_decrypt",
     "jfsx_data_encrypt_ex", "jfsx_data_decrypt_ex", "jfsx_agg_data_encrypt_ex", "jfsx_agg_data_decrypt_ex",
+    "jfsx_file_checksum_span", "jfsx_file_checksum_batch", "jfsx_file_checksum_fold",
 ]
 
 
@@ -100,6 +101,13 @@ class jfsx_zblk(ctypes.Structure):
         ("src", ctypes.c_void_p), ("src_len", ctypes.c_uint64), ("dst", ctypes.c_void_p),
         ("dst_cap", ctypes.c_uint64), ("out_len", ctypes.c_uint64), ("status", ctypes.c_int32),
         ("reserved", ctypes.c_int32),
+    ]
+
+
+class jfsx_fsum(ctypes.Structure):
+    _fields_ = [
+        ("data", ctypes.c_void_p), ("len", ctypes.c_uint64), ("md5", ctypes.c_uint8 * 16),
+        ("bytes_per_crc", ctypes.c_uint32), ("crc32c", ctypes.c_uint32), ("crc_per_block", ctypes.c_uint64),
     ]
 
 
@@ -163,6 +171,9 @@ def load_library(path=LIB_PATH):
             "jfsx_open_batch": (I, [P, I, I, ctypes.POINTER(jfsx_blk), I, I]),
             "jfsx_crc32c_segments": (I, [P, I, ctypes.POINTER(jfsx_range), I, I]),
             "jfsx_checksum": (I, [P, P, U64, P]),
+            "jfsx_file_checksum_span": (U64, [U64, U64, U32]),
+            "jfsx_file_checksum_batch": (I, [P, I, ctypes.POINTER(jfsx_fsum), U32, U64, I]),
+            "jfsx_file_checksum_fold": (I, [P, U64, U64, U32, U64, ctypes.POINTER(jfsx_fsum)]),
             "jfsx_cache_verify": (I, [P, P, U64, U64, I, U64, U64, P, ctypes.POINTER(U64),
                                       ctypes.POINTER(U32), ctypes.POINTER(U32), ctypes.POINTER(ctypes.c_int64)]),
             "jfsx_data_encrypt": (I, [P, I, P, P, P, I, P, U64, P, U64, ctypes.POINTER(U64), P]),
@@ -270,6 +281,28 @@ def lz4_bound(n):
 def zstd_bound(n):
     """ZSTD_compressBound (compress.go:80 CompressBound)."""
     return load_library().jfsx_zstd_bound(n)
+
+
+def file_checksum_span(file_size, length, bytes_per_crc=512):
+    """jfsx_file_checksum_span: the bytes getFileChecksum(f, length) hashes of a file of file_size."""
+    return load_library().jfsx_file_checksum_span(file_size, length, bytes_per_crc)
+
+
+def _fsum_result(f):
+    """(crc32c flag, bytesPerCRC, crcPerBlock, md5 bytes) of a filled jfsx_fsum"""
+    return int(f.crc32c), int(f.bytes_per_crc), int(f.crc_per_block), bytes(f.md5)
+
+
+def file_checksum_fold(chunk_crcs, span_len, block_bytes=128 << 20, bytes_per_crc=512):
+    """jfsx_file_checksum_fold (host only): the block and file MD5s over the
+    big-endian chunk CRCs of a span of span_len bytes."""
+    cc = _u8(chunk_crcs)
+    f = jfsx_fsum()
+    rc = load_library().jfsx_file_checksum_fold(cc.ctypes.data if cc.size else None, cc.size // 4, span_len,
+                                                bytes_per_crc, block_bytes, ctypes.byref(f))
+    if rc:
+        raise EngineError(rc, "jfsx_file_checksum_fold")
+    return _fsum_result(f)
 
 
 def device_numa_node(device):
@@ -450,6 +483,21 @@ class Engine:
 
     def crc32c_segments(self, ranges, n, mode=CRC_GEN, mem=MEM_DEVICE):
         self._check(self.L.jfsx_crc32c_segments(self.ctx, n, ranges, mode, mem), "jfsx_crc32c_segments")
+
+    def file_checksum_batch(self, files, block_bytes=128 << 20, bytes_per_crc=512, mem=MEM_DEVICE):
+        """jfsx_file_checksum_batch: Hadoop's MD5-of-MD5-of-CRC32C of every
+        file's span in one call.  files: (data, nbytes) pairs -- data a
+        DeviceBuffer or device address (MEM_DEVICE), a numpy array or host
+        address (MEM_HOST).  Returns one (crc32c flag, bytesPerCRC,
+        crcPerBlock, md5 bytes) per file."""
+        files = list(files)
+        arr = (jfsx_fsum * max(len(files), 1))()
+        for i, (data, nbytes) in enumerate(files):
+            arr[i].data = _ptr(data) if nbytes else None
+            arr[i].len = nbytes
+        self._check(self.L.jfsx_file_checksum_batch(self.ctx, len(files), arr, bytes_per_crc, block_bytes, mem),
+                    "jfsx_file_checksum_batch")
+        return [_fsum_result(arr[i]) for i in range(len(files))]
 
     # -- LZ4 stage (jfsx_lz4_*) -------------------------------------------
     @staticmethod
