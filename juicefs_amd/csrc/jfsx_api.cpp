@@ -307,8 +307,12 @@ void make_crc_chunk_mul(std::vector<uint32_t> &m, uint32_t *k512) {
 inline uint64_t nseg_of(uint64_t len) { return len ? (len + kSeg - 1) / kSeg : 1; }
 
 struct Plan {
-    std::vector<Task> tasks;
+    std::vector<Task> tasks;  // in plan order: block by block, c0 ascending
     uint64_t nslots = 0;
+    uint64_t task_bytes = 0;  // every task but a block's last has this many bytes
+    int kind = 0;
+    // the tasks in the order the kernel is given them (plan_batch)
+    void dispatch(Task *out) const;
 };
 
 // Device + pinned-host scratch for one in-flight batch.
@@ -532,6 +536,7 @@ Plan plan_tasks(const std::vector<uint64_t> &lens, uint64_t max_bytes, uint32_t 
         uint64_t c = (total / want + unit - 1) / unit * unit;
         ch = std::max(unit, std::min(ch, c));
     }
+    p.task_bytes = ch;
     for (size_t b = 0; b < lens.size(); b++) {
         for (uint64_t c0 = 0; c0 < lens[b]; c0 += ch) {
             Task t;
@@ -570,6 +575,50 @@ constexpr uint64_t kCpMaxLen = ((uint64_t)1 << 38) - 64;
 uint64_t crc_task_bytes(uint64_t total) {
     const uint64_t round = 16 * (uint64_t)kSeg;
     return std::min<uint64_t>(kCrcTaskBytes, std::max<uint64_t>(round, (total / 512 + round - 1) / round * round));
+}
+
+// The task list of a batch: the one place that chooses it, for the AEAD
+// transforms (enqueue_aead), for crc_segments_k (enqueue_crc, the ciphertext
+// pass of JFSX_CRC_BOTH, the file checksum's rounds) and for jfsx_debug_plan.
+// It depends on the blocks' lengths alone.
+//   GCM:    a small batch (the per-object path) is cut into tasks down to
+//           64 KiB so that it still spreads over the CUs (2 tasks per CU); a
+//           64 GiB batch keeps 4 MiB tasks
+//   ChaCha: 128 KiB (one segment per wave) to 1 MiB, 8 tasks per CU
+//   CRC:    crc_task_bytes; no partial slots
+enum { kPlanGcm = 0, kPlanCp = 1, kPlanCrc = 2 };
+
+Plan plan_batch(int kind, const std::vector<uint64_t> &lens) {
+    Plan p;
+    if (kind == kPlanGcm) {
+        p = plan_tasks(lens, kMaxTaskBytes, kWaves, kSlotsPerTask, 512, kGcmMinTask);
+    } else if (kind == kPlanCp) {
+        p = plan_tasks(lens, kCpTaskBytes, kCpWaves, kCpWaves, 2048);
+    } else {
+        uint64_t total = 0;
+        for (uint64_t l : lens) total += l;
+        const uint64_t per = crc_task_bytes(total);
+        p.task_bytes = per;
+        for (size_t i = 0; i < lens.size(); i++)
+            for (uint64_t c0 = 0; c0 < lens[i]; c0 += per)
+                p.tasks.push_back(Task{(uint32_t)i, 0, c0, std::min(c0 + per, lens[i])});
+    }
+    p.kind = kind;
+    return p;
+}
+
+// The persistent transform kernels take tasks in array order: largest first,
+// so that the last tasks handed out are short (slots stay per task).  A
+// counting sort on 4 KiB units: O(n), on the host's critical path for every
+// batch.  crc_segments_k is one workgroup per task (no queue): plan order.
+void Plan::dispatch(Task *out) const {
+    if (tasks.empty()) return;
+    memcpy(out, tasks.data(), sizeof(Task) * tasks.size());
+    if (kind == kPlanCrc) return;
+#ifdef JFSX_ABLATE_TRACE
+    for (size_t t = 0; t < tasks.size(); t++) out[t].trace = (uint32_t)t;
+#endif
+    order_largest_first(out, tasks.size(), (size_t)(kind == kPlanGcm ? kMaxTaskBytes : kCpTaskBytes) >> 12);
 }
 
 int check_aead_args(int algo, int n, const jfsx_blk *blks, int crc_mode, bool device) {
@@ -631,22 +680,13 @@ int enqueue_aead(jfsx_ctx *c, Workspace &w, hipStream_t s, hipEvent_t k0, hipEve
         if ((crc_mode & 3) == JFSX_CRC_VERIFY) crc_calc_words += nseg_of(blks[i].len);
         crc_words += mult * nseg_of(blks[i].len);
     }
-    std::vector<Task> ctasks;  // the ciphertext pass (BOTH)
-    if (both) {
-        uint64_t total = 0;
-        for (int i = 0; i < n; i++) total += lens[i];
-        const uint64_t per = crc_task_bytes(total);
-        for (int i = 0; i < n; i++)
-            for (uint64_t c0 = 0; c0 < lens[i]; c0 += per) ctasks.push_back(Task{(uint32_t)i, 0, c0, std::min(c0 + per, lens[i])});
-    }
+    Plan cplan;  // the ciphertext pass (BOTH)
+    if (both) cplan = plan_batch(kPlanCrc, lens);
+    const std::vector<Task> &ctasks = cplan.tasks;
     const bool hc_in = host_crc && (crc_mode & 3) == JFSX_CRC_VERIFY;
     const bool hc_out = host_crc && (crc_mode & 3) == JFSX_CRC_GEN;
     const uint32_t slots = gcm ? kSlotsPerTask : kCpWaves;
-    // a small batch (the per-object path) is cut into tasks down to 64 KiB so
-    // that it still spreads over the CUs (2 tasks per CU); a 64 GiB batch keeps
-    // 4 MiB tasks
-    Plan plan = gcm ? plan_tasks(lens, kMaxTaskBytes, kWaves, slots, 512, kGcmMinTask)
-                    : plan_tasks(lens, kCpTaskBytes, kCpWaves, slots, 2048);
+    const Plan plan = plan_batch(gcm ? kPlanGcm : kPlanCp, lens);
     const size_t nt = plan.tasks.size();
     // device workspace layout
     size_t off = 0;
@@ -717,19 +757,8 @@ int enqueue_aead(jfsx_ctx *c, Workspace &w, hipStream_t s, hipEvent_t k0, hipEve
         bd.nslots += slots;
         max_slots = std::max(max_slots, bd.nslots);
     }
-    if (nt) {
-        Task *ht = (Task *)(h + o_task);
-        memcpy(ht, plan.tasks.data(), sizeof(Task) * nt);
-#ifdef JFSX_ABLATE_TRACE
-        for (size_t t = 0; t < nt; t++) ht[t].trace = (uint32_t)t;
-#endif
-        // the persistent transform kernels take tasks in array order: largest
-        // first, so that the last tasks handed out are short (slots stay per
-        // task).  A counting sort on 4 KiB units: O(n), on the host's
-        // critical path for every batch
-        order_largest_first(ht, nt, (size_t)(gcm ? kMaxTaskBytes : kCpTaskBytes) >> 12);
-    }
-    if (!ctasks.empty()) memcpy(h + o_ctask, ctasks.data(), sizeof(Task) * ctasks.size());
+    plan.dispatch((Task *)(h + o_task));
+    cplan.dispatch((Task *)(h + o_ctask));
     // the ciphertext pass of BOTH on stream st
     auto ct_pass = [&](hipStream_t st) {
         launch_crc_segments(st, (int)ctasks.size(), (const Task *)(d + o_ctask), (const BlkDev *)(d + o_cblk), c->tabs);
@@ -913,17 +942,15 @@ std::vector<std::pair<int, int>> host_groups(const jfsx_ctx *c, int n, const jfs
 int enqueue_crc(jfsx_ctx *c, Workspace &w, hipStream_t s, hipEvent_t k0, hipEvent_t k1, int n, const jfsx_blk *blks,
                 int mode, hipStream_t up = nullptr, hipEvent_t up_ev = nullptr, bool collect = true,
                 bool host_crc = false, bool zc = false) {
-    uint64_t total = 0, calc_words = 0, crc_words = 0;
+    uint64_t calc_words = 0, crc_words = 0;
+    std::vector<uint64_t> lens(n);
     for (int i = 0; i < n; i++) {
-        total += blks[i].len;
+        lens[i] = blks[i].len;
         crc_words += nseg_of(blks[i].len);
         if (mode == JFSX_CRC_VERIFY) calc_words += nseg_of(blks[i].len);
     }
-    const uint64_t per = crc_task_bytes(total);
-    std::vector<Task> tasks;
-    for (int i = 0; i < n; i++)
-        for (uint64_t c0 = 0; c0 < blks[i].len; c0 += per)
-            tasks.push_back(Task{(uint32_t)i, 0, c0, std::min(c0 + per, blks[i].len)});
+    const Plan plan = plan_batch(kPlanCrc, lens);
+    const std::vector<Task> &tasks = plan.tasks;
     const bool hc_in = host_crc && mode == JFSX_CRC_VERIFY, hc_out = host_crc && mode == JFSX_CRC_GEN;
     const size_t nt = tasks.size();
     size_t off = 0;
@@ -960,7 +987,7 @@ int enqueue_crc(jfsx_ctx *c, Workspace &w, hipStream_t s, hipEvent_t k0, hipEven
             calc += nseg_of(b.len);
         }
     }
-    if (nt) memcpy(h + o_task, tasks.data(), sizeof(Task) * nt);
+    plan.dispatch((Task *)(h + o_task));
     BlkOut *dout = zc ? (BlkOut *)(h + o_hres) : (BlkOut *)(d + o_out);
     launch_begin();
     if (zc) launch_pull(s, d, h, h_bytes);
@@ -2334,12 +2361,9 @@ int run_file_checksum(jfsx_ctx *c, int n, jfsx_fsum *f, uint64_t block_bytes, bo
     std::vector<std::vector<Task>> rtasks(rounds.size());
     size_t max_tasks = 1, max_pieces = 1;
     for (size_t r = 0; r < rounds.size(); r++) {
-        uint64_t total = 0;
-        for (const FsumPiece &p : rounds[r]) total += p.len;
-        const uint64_t tb = crc_task_bytes(total);
-        for (size_t k = 0; k < rounds[r].size(); k++)
-            for (uint64_t c0 = 0; c0 < rounds[r][k].len; c0 += tb)
-                rtasks[r].push_back(Task{(uint32_t)k, 0, c0, std::min(c0 + tb, rounds[r][k].len)});
+        std::vector<uint64_t> lens;
+        for (const FsumPiece &p : rounds[r]) lens.push_back(p.len);
+        rtasks[r] = plan_batch(kPlanCrc, lens).tasks;
         max_tasks = std::max(max_tasks, rtasks[r].size());
         max_pieces = std::max(max_pieces, rounds[r].size());
     }
@@ -2867,6 +2891,28 @@ void jfsx_gen_key(uint64_t seed, uint64_t b, uint8_t key[32], uint8_t nonce[12])
     uint64_t w1 = mix64((seed ^ 0x4E4F4E4345ULL) + G * ((b << 8) + 2));
     memcpy(nonce, &w0, 8);
     memcpy(nonce + 8, &w1, 4);
+}
+
+// Host-only view of plan_batch (no device, no context), for tests: kind 0 GCM,
+// 1 ChaCha20-Poly1305, 2 CRC-only; tasks (nullable): up to cap triples
+// (blk, c0, c1) in dispatch order.  Not part of the ABI (undeclared in jfsx.h).
+int jfsx_debug_plan(int kind, int n, const uint64_t *lens, uint64_t *task_bytes, uint64_t *ntasks, uint64_t *nslots,
+                    uint64_t *tasks, uint64_t cap) {
+    if (kind < kPlanGcm || kind > kPlanCrc || n < 0 || (n && !lens)) return JFSX_EINVAL;
+    const Plan p = plan_batch(kind, std::vector<uint64_t>(lens, lens + n));
+    if (task_bytes) *task_bytes = p.task_bytes;
+    if (ntasks) *ntasks = p.tasks.size();
+    if (nslots) *nslots = p.nslots;
+    if (tasks && cap) {
+        std::vector<Task> t(std::max<size_t>(p.tasks.size(), 1));
+        p.dispatch(t.data());
+        for (size_t i = 0; i < std::min<uint64_t>(cap, p.tasks.size()); i++) {
+            tasks[3 * i] = t[i].blk;
+            tasks[3 * i + 1] = t[i].c0;
+            tasks[3 * i + 2] = t[i].c1;
+        }
+    }
+    return 0;
 }
 
 int jfsx_debug_tables(uint32_t *aes, uint32_t *crc, uint32_t *crcx) {

@@ -266,6 +266,33 @@ def debug_tables():
     return aes, crc, crcx
 
 
+PLAN_GCM, PLAN_CHACHA, PLAN_CRC = 0, 1, 2
+
+
+def debug_plan(kind, lens):
+    """How the engine would cut a device batch of blocks of these lengths into
+    tasks (host only, no device; jfsx_debug_plan is a test hook outside the
+    ABI).  kind: PLAN_GCM, PLAN_CHACHA or PLAN_CRC (crc_segments_k).  Returns
+    (task_bytes, nslots, tasks) with tasks the (blk, c0, c1) triples in
+    dispatch order."""
+    fn = load_library().jfsx_debug_plan
+    U64P = ctypes.POINTER(ctypes.c_uint64)
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, U64P, U64P, U64P, ctypes.c_void_p, ctypes.c_uint64]
+    ln = np.ascontiguousarray(lens, dtype=np.uint64)
+    tb, nt, ns = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    rc = fn(kind, ln.size, ln.ctypes.data if ln.size else None, ctypes.byref(tb), ctypes.byref(nt), ctypes.byref(ns),
+            None, 0)
+    if rc:
+        raise EngineError(rc, "jfsx_debug_plan")
+    tasks = np.zeros((nt.value, 3), np.uint64)
+    if nt.value:
+        rc = fn(kind, ln.size, ln.ctypes.data, None, None, None, tasks.ctypes.data, nt.value)
+        if rc:
+            raise EngineError(rc, "jfsx_debug_plan")
+    return tb.value, ns.value, [tuple(int(x) for x in t) for t in tasks]
+
+
 def gen_key(seed, block):
     key = np.empty(32, np.uint8)
     nonce = np.empty(12, np.uint8)
