@@ -19,6 +19,8 @@
  *   jfsx_cache_verify    cacheFile.ReadAt level logic + verify      pkg/chunk/disk_cache.go:1255-1329
  *   jfsx_object_crc32c   generateChecksum / checksumReader of the   pkg/object/checksum.go:31-82
  *   (+ JFSX_CRC_CT)      stored object, fused with Seal/Open        (s3.go:140-146,173-176)
+ *   jfsx_load_batch      cachedStore.load's Decrypt + Decompress +  pkg/chunk/cached_store.go:673-748
+ *                        bcache.cache's checksum(), one call        (disk_cache.go:433-483)
  *   JFSX_AES256GCM /     NewDataEncryptor algo "aes256gcm-rsa" /    pkg/object/encrypt.go:142-162
  *   JFSX_CHACHA20P1305   "chacha20-rsa"
  *
@@ -506,6 +508,59 @@ uint64_t jfsx_zstd_bound(uint64_t n); /* ZSTD_compressBound */
 int jfsx_zstd_compress_batch(jfsx_ctx *ctx, int n, jfsx_zblk *blks, int mem);
 int jfsx_agg_zstd_compress(jfsx_agg *agg, jfsx_zblk *blk, int mem);
 int jfsx_mctx_zstd_compress_batch(jfsx_mctx *m, int n, jfsx_zblk *blks, int mem);
+
+/* One-call block load: the read miss of a volume formatted with --compress
+ * lz4 / zstd (cachedStore.load, pkg/chunk/cached_store.go:673-748) -- Decrypt
+ * (encrypt.go:196-216), Decompress into the page (cached_store.go:738) and
+ * bcache.cache's checksum() (disk_cache.go:433-483) -- for a batch of stored
+ * block images in one synchronous call.  Every intermediate stays in device
+ * memory: JFSX_MEM_HOST moves each image up once and each page (with its CRC
+ * array) down once, JFSX_MEM_DEVICE synchronises the stream once.  A decoder is
+ * never started on bytes whose tag has not verified.
+ *   algo      JFSX_AES256GCM, JFSX_CHACHA20P1305, or JFSX_CIPHER_NONE for a
+ *             volume without --encrypt-rsa-key (src is the compressed block)
+ *   codec     JFSX_CODEC_LZ4 or JFSX_CODEC_ZSTD (a volume with no codec is
+ *             served by jfsx_open_batch with JFSX_CRC_GEN)
+ *   crc_mode  JFSX_CRC_NONE or JFSX_CRC_GEN
+ *   mem       JFSX_MEM_DEVICE: jfsx_blk's alignment rule where the AEAD and
+ *             CRC kernels touch a buffer -- src 16-byte aligned with a cipher,
+ *             dst 16-byte aligned with JFSX_CRC_GEN -- and dst distinct from
+ *             src; JFSX_MEM_HOST: pageable or pinned memory at any alignment
+ * Limits (JFSX_EINVAL beyond them, before anything runs): src_len <=
+ * 0x7E000000, len < 2^32, and len < 2^31 for zstd.  Per-block result, the
+ * first rule that applies:
+ *   tag does not verify           JFSX_ETAG                          out_len 0
+ *   decoder rejects the image     JFSX_EFORMAT (LZ4: also an image that
+ *                                 decodes to more than len bytes), or
+ *                                 JFSX_EDSTSIZE (zstd frame larger than len)
+ *                                                                    out_len 0
+ *   decoder produced n < len      JFSX_ESHORT                        out_len n
+ *   otherwise                     JFSX_OK                            out_len len
+ * On any status other than JFSX_OK the page (dst[0, len)) and the CRC array
+ * are all zero when the call returns.  len == 0 is legal: the image must decode
+ * to nothing, and the CRC array is 4 zero bytes, as checksum() gives.  The call
+ * is counted in jfsx_metrics as the separate calls would be: open_* (unless
+ * JFSX_CIPHER_NONE), lz4d_* / zstdd_* over the blocks that reached the decoder
+ * (those whose tag verified), crc_* over the n pages (with JFSX_CRC_GEN). */
+#define JFSX_CIPHER_NONE (-1) /* algo: the volume has no --encrypt-rsa-key      */
+#define JFSX_CODEC_LZ4 1      /* compress.go:104-125                            */
+#define JFSX_CODEC_ZSTD 2     /* compress.go:93-102                             */
+#define JFSX_ESHORT 6 /* per-block: decoded n < len ("read %s fully: %s (%d < %d)", cached_store.go:740-743) */
+typedef struct jfsx_lblk {
+    uint8_t key[32];      /* as jfsx_blk; ignored with JFSX_CIPHER_NONE       */
+    uint8_t nonce[12];
+    uint32_t reserved;    /* must be 0                                        */
+    uint8_t tag[16];      /* in; ignored with JFSX_CIPHER_NONE                */
+    const void *src;      /* stored image: C without header and tag, or the compressed block itself */
+    uint64_t src_len;
+    void *dst;            /* the page                                         */
+    uint64_t len;         /* page length = block size the key names (cached_store.go:938-942) */
+    uint8_t *crc;         /* CRC_GEN: out, 4*max(1,ceil(len/32K)) bytes; unused with CRC_NONE */
+    uint64_t out_len;     /* out: bytes the decoder produced (0 unless it ran) */
+    int32_t status;       /* out                                              */
+    int32_t codec_info;   /* out: zstd, why the serial decoder took it (as jfsx_zblk.reserved) */
+} jfsx_lblk;
+int jfsx_load_batch(jfsx_ctx *ctx, int algo, int codec, int n, jfsx_lblk *blks, int crc_mode, int mem);
 
 /* header helper: returns wrapped-key length and offset/size of the nonce so a
  * caller can unwrap the key first (encrypt.go:197-205) */

@@ -17,7 +17,9 @@ reference binds; CompressBatch / DecompressBatch are the batched entry points
 (one engine call per batch).  Zstandard runs on the engine both ways:
 jfsx_zstd_compress_batch (jfsx_zstdc.hip) writes the zstd library's level-1
 frames byte for byte, jfsx_zstd_decompress_batch (jfsx_zstd.hip) decodes as
-ZSTD_decompress.
+ZSTD_decompress.  load_blocks_fused is load_block as one engine call
+(jfsx_load_batch: Decrypt, Decompress and the cache's checksum() chained in
+device memory).
 """
 from . import engine as E
 from .encrypt import default_engine
@@ -263,3 +265,94 @@ def load_blocks(store, keys, lengths, compressor):
             raise CompressError("read %s fully: %s (%d < %d)" % (k, None, len(d), n))
         out.append(d)
     return out
+
+
+def load_blocks_fused(store, keys, lengths, compressor, enc=None, checksums=True):
+    """cachedStore.load for a batch in one engine call (jfsx_load_batch): the
+    raw objects of `store` are opened (with enc, a DataEncryptor: header parse
+    and batched key unwrap on the way), decompressed into pages of the blocks'
+    lengths and checksummed without leaving the device in between
+    (cached_store.go:673-748; bcache.cache's checksum(), disk_cache.go:433-483).
+
+    Returns what load_blocks(NewEncrypted(store, enc) or store, ...) returns,
+    and raises what it raises: a decrypt failure of any object first
+    ("Decrypt: ..." as Encrypted.Get wraps DataEncryptor.Decrypt's error), then,
+    in key order, "read %s fully: %s (%d < %d)".  With checksums=True the result
+    is (pages, crcs): crcs[i] is checksum(pages[i]), the trailer write_cache_file
+    appends."""
+    from .encrypt import _ERR_OPEN, EncryptError
+    if not isinstance(compressor, (LZ4, ZStandard)):
+        raise ValueError("load_blocks_fused needs the lz4 or zstd compressor (an uncompressed volume loads "
+                         "through DataEncryptor.DecryptBatch)")
+    lz4 = isinstance(compressor, LZ4)
+    empty = "decompress an empty input" if lz4 else "Bytes slice is empty"
+    eng = compressor.eng
+    objs = [store.Get(k, 0, -1) for k in keys]
+    lengths = [int(n) for n in lengths]
+    dec_err = [None] * len(keys)  # per block: the error Decrypt would return
+    items = [None] * len(keys)
+    if enc is None:
+        algo = E.CIPHER_NONE
+        for k, o, n in zip(keys, objs, lengths):
+            if len(o) == 0:  # LZ4.Decompress / zstd.Decompress reject it before the codec runs
+                raise CompressError("read %s fully: %s (%d < %d)" % (k, empty, 0, n))
+        items = list(objs)
+    else:
+        algo = enc.algo
+        parsed = []
+        for i, c in enumerate(objs):
+            c = bytes(c)
+            if len(c) < 3:
+                dec_err[i] = "misformed ciphertext: 0 0"
+                continue
+            keyLen, nonceLen = (c[0] << 8) + c[1], c[2]
+            if 3 + keyLen + nonceLen >= len(c):
+                dec_err[i] = "misformed ciphertext: %d %d" % (keyLen, nonceLen)
+                continue
+            parsed.append((i, c, keyLen, nonceLen))
+        wrapped = [c[3:3 + kl] for _, c, kl, _ in parsed]
+        if hasattr(enc.keyEncryptor, "DecryptBatch"):
+            dkeys = enc.keyEncryptor.DecryptBatch(wrapped, eng)
+        else:
+            dkeys = []
+            for w in wrapped:
+                try:
+                    dkeys.append(enc.keyEncryptor.Decrypt(w))
+                except Exception as e:
+                    dkeys.append(e)
+        for (i, c, keyLen, nonceLen), key in zip(parsed, dkeys):
+            nonce, ct = c[3 + keyLen:3 + keyLen + nonceLen], c[3 + keyLen + nonceLen:]
+            if isinstance(key, Exception):
+                dec_err[i] = "decryt key: " + str(key)
+            elif len(key) != enc.keyLen:
+                dec_err[i] = "crypto/aes: invalid key size %d" % len(key)
+            elif nonceLen != 12 or len(ct) < 16:
+                dec_err[i] = _ERR_OPEN[algo]
+            else:
+                items[i] = (key, nonce, ct[:-16], ct[-16:])
+    for e in dec_err:
+        if e is not None:
+            raise EncryptError("Decrypt: %s" % e)
+    res = eng.load(algo, E.CODEC_LZ4 if lz4 else E.CODEC_ZSTD, items, lengths, crc=checksums)
+    info = eng.load_info
+    for st, _, _ in res:
+        if st == E.ETAG:
+            raise EncryptError("Decrypt: %s" % _ERR_OPEN[algo])
+    pages, crcs = [], []
+    for i, (k, n, (st, page, crc)) in enumerate(zip(keys, lengths, res)):
+        if enc is not None and len(items[i][2]) == 0:
+            raise CompressError("read %s fully: %s (%d < %d)" % (k, empty, 0, n))
+        if st == E.EDSTSIZE:
+            # the text names the decoded size: decode this object alone into a
+            # buffer that holds it, as ZStandard.DecompressBatch does
+            blob = objs[i] if enc is None else enc.Decrypt(objs[i])
+            d = compressor.DecompressBatch([blob], [n])[0]
+            raise CompressError("read %s fully: %s (%d < %d)" % (k, d, 0, n))
+        if st == E.EFORMAT:
+            raise CompressError("read %s fully: %s (%d < %d)"
+                                % (k, "lz4: malformed block" if lz4 else "zstd: corrupted frame", 0, n))
+        if st == E.ESHORT:
+            raise CompressError("read %s fully: %s (%d < %d)" % (k, None, info[i][0], n))
+        pages.append(page)
+        crcs.append(crc)
+    return (pages, crcs) if checksums else pages

@@ -417,6 +417,21 @@ struct jfsx_ctx {
     size_t rsa_dcap = 0;
     char *rsa_h = nullptr;  // pinned mirror of ct in / em + len out
     size_t rsa_hcap = 0;
+    // jfsx_load_batch (run_load): its own grow-only buffers, so that no stage
+    // overwrites what an earlier one left.  load_aead / load_crc are the
+    // workspaces enqueue_aead (Open) and enqueue_crc plan into; load_d holds
+    // LoadBlk | ZDev | ZOut | LoadRes | CRC words | the zstd decoder's arenas,
+    // load_h its pinned mirror (LoadBlk up, LoadRes and CRC words down);
+    // load_stage the images and pages of a host batch, or the opened images of
+    // a device batch.
+    Workspace load_aead, load_crc;
+    char *load_d = nullptr;
+    size_t load_dcap = 0;
+    char *load_h = nullptr;
+    size_t load_hcap = 0;
+    char *load_stage = nullptr;
+    size_t load_scap = 0;
+    hipEvent_t load_ev[4] = {};  // main-kernel timing of its Open and CRC stages
     double ms_total = 0;
     uint64_t launches = 0;
     BouncePool bounce;       // pinned staging of pageable caller memory (host calls)
@@ -1606,6 +1621,41 @@ uint64_t zstd_bound(uint64_t n) { return n + (n >> 8) + (n < (128u << 10) ? ((12
 
 enum CodecOp { kLz4Comp, kLz4Decomp, kZstdDecomp, kZstdComp };
 
+// Waves of the zstd decoder for a batch of n objects (run_codec and run_load):
+// block-parallel persistent waves unless JFSX_ZSTD_SERIAL=1 selects the
+// one-wave-per-object serial kernel (A/B; 0 = serial).  The waves are capped by
+// the context's arena budget (a 64-object batch needs 64 arenas, not 8 per CU).
+int zstd_decode_waves(const jfsx_ctx *c, int n) {
+    static const bool zd_serial = getenv("JFSX_ZSTD_SERIAL") && atoi(getenv("JFSX_ZSTD_SERIAL")) == 1;
+    int waves = !zd_serial ? zstd_par_waves(n, c->ncu) : 0;
+    if (waves) waves = (int)std::min<size_t>((size_t)waves, std::max<size_t>(c->zstd_arena_budget / kZstdArena, 1));
+    return waves;
+}
+
+// Grow *buf to `base` bytes plus the zstd decoder's scratch for n objects:
+// *waves arenas, or n x kZstdScratch (128 KiB per object) for the serial
+// kernel.  If the buffer cannot grow to that many arenas, fewer waves are
+// tried, then the serial kernel; *waves is what fitted.  A hipMalloc failure
+// the fallback recovers from is not recorded as the batch's error.
+int ensure_zstd_decode(jfsx_ctx *c, char **buf, size_t *cap, size_t base, int n, int *waves) {
+    ErrRec before;
+    {
+        std::lock_guard<std::mutex> g(c->err_mu);
+        before = c->err;
+    }
+    for (;;) {
+        const size_t extra = *waves ? kZstdArena * (size_t)*waves : kZstdScratch * (size_t)n;
+        const int rc = ensure_dev(c, buf, cap, base + extra);
+        if (rc != JFSX_ENOMEM || *waves == 0) return rc;
+        *waves = *waves > c->ncu ? std::max(*waves / 2, c->ncu) : 0;  // fewer waves, then serial
+        (void)hipGetLastError();  // the failed hipMalloc is not this batch's error
+        {
+            std::lock_guard<std::mutex> g(c->err_mu);
+            c->err = before;
+        }
+    }
+}
+
 // The codec stages (jfsx_lz4.hip, jfsx_zstd.hip, jfsx_zstdc.hip): one wave per
 // object.  Host-memory batches are staged through the context's slot-0
 // staging buffer (inputs up, the out_len bytes of each output down).
@@ -1628,34 +1678,18 @@ int run_codec(jfsx_ctx *c, int n, jfsx_zblk *z, int mem, CodecOp op) {
                                                          : kZcWavesPerCu;
     const int zc_waves = std::min(n, c->ncu * zc_per_cu);
     static const bool zc_queue = getenv("JFSX_ZC_QUEUE") && atoi(getenv("JFSX_ZC_QUEUE")) == 1;
-    // zstd decompression: block-parallel persistent waves unless
-    // JFSX_ZSTD_SERIAL=1 selects the one-wave-per-object serial kernel (A/B)
-    static const bool zd_serial = getenv("JFSX_ZSTD_SERIAL") && atoi(getenv("JFSX_ZSTD_SERIAL")) == 1;
-    // the block-parallel decoder's waves are capped by the context's arena
-    // budget (a 64-object batch needs 64 arenas, not 8 per CU); if the
-    // workspace cannot grow to that many, fewer waves are tried, then the
-    // serial kernel, whose scratch is n x kZstdScratch (128 KiB per object)
-    int zd_waves = op == kZstdDecomp && !zd_serial ? zstd_par_waves(n, c->ncu) : 0;
-    if (zd_waves) zd_waves = (int)std::min<size_t>((size_t)zd_waves, std::max<size_t>(c->zstd_arena_budget / kZstdArena, 1));
+    // zstd decompression: the decoder's waves and arenas (zstd_decode_waves,
+    // ensure_zstd_decode: fewer waves, then the serial kernel, under memory
+    // pressure)
+    int zd_waves = op == kZstdDecomp ? zstd_decode_waves(c, n) : 0;
     const size_t o_out = align256(sizeof(ZDev) * n), o_tab = o_out + align256(sizeof(ZOut) * n);
-    ErrRec before;  // a hipMalloc failure the arena fallback recovers from is not recorded
-    {
-        std::lock_guard<std::mutex> g(c->err_mu);
-        before = c->err;
-    }
-    for (;;) {
+    if (op == kZstdDecomp) {
+        rc = ensure_zstd_decode(c, &w.d, &w.dcap, o_tab, n, &zd_waves);
+    } else {
         size_t extra = 0;
         if (op == kLz4Comp) extra = kLz4TabBytes * (size_t)n;
-        else if (op == kZstdDecomp) extra = zd_waves ? kZstdArena * (size_t)zd_waves : kZstdScratch * (size_t)n;
         else if (op == kZstdComp) extra = 256 + kZstdcScratch * (size_t)zc_waves;  // per-wave scratch
         rc = ensure_dev(c, &w.d, &w.dcap, o_tab + extra);
-        if (rc != JFSX_ENOMEM || op != kZstdDecomp || zd_waves == 0) break;
-        zd_waves = zd_waves > c->ncu ? std::max(zd_waves / 2, c->ncu) : 0;  // fewer waves, then serial
-        (void)hipGetLastError();  // the failed hipMalloc is not this batch's error
-        {
-            std::lock_guard<std::mutex> g(c->err_mu);
-            c->err = before;
-        }
     }
     if (rc) return rc;
     if ((rc = ensure_host(&w.h, &w.hcap, o_tab))) return rc;  // descriptors and results only
@@ -1725,6 +1759,295 @@ int run_codec(jfsx_ctx *c, int n, jfsx_zblk *z, int mem, CodecOp op) {
             HIP_OK(hipMemcpyAsync(z[i].dst, sdst[i], ho[i].out_len, hipMemcpyDeviceToHost, s));
     }
     if (mem == JFSX_MEM_HOST) HIP_OK(hipStreamSynchronize(s));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// jfsx_load_batch: Open -> decompress -> checksum() of a batch of stored block
+// images in one call (cachedStore.load, cached_store.go:673-748).  The stages
+// are enqueued on the context's stream back to back (jfsx_load.hip has the
+// order and the gate rule); the host plans everything from the lengths alone,
+// so it waits once, at the end.
+// ---------------------------------------------------------------------------
+int check_load_args(int algo, int codec, int n, const jfsx_lblk *blks, int crc_mode, int mem) {
+    if (algo != JFSX_AES256GCM && algo != JFSX_CHACHA20P1305 && algo != JFSX_CIPHER_NONE) return JFSX_EINVAL;
+    if (codec != JFSX_CODEC_LZ4 && codec != JFSX_CODEC_ZSTD) return JFSX_EINVAL;
+    if (crc_mode != JFSX_CRC_NONE && crc_mode != JFSX_CRC_GEN) return JFSX_EINVAL;
+    if (mem != JFSX_MEM_DEVICE && mem != JFSX_MEM_HOST) return JFSX_EINVAL;
+    if (n < 0) return JFSX_EINVAL;
+    for (int i = 0; i < n; i++) {
+        const jfsx_lblk &b = blks[i];
+        if ((b.src_len && !b.src) || (b.len && !b.dst)) return JFSX_EINVAL;
+        // run_codec's limits, then the ciphers' (check_aead_args)
+        if (b.src_len > kLz4MaxInput || b.len >= ((uint64_t)1 << 32)) return JFSX_EINVAL;
+        if (codec == JFSX_CODEC_ZSTD && b.len >= ((uint64_t)1 << 31)) return JFSX_EINVAL;  // 32-bit frame positions
+        if (algo == JFSX_AES256GCM && b.src_len > kGcmMaxLen) return JFSX_EINVAL;
+        if (algo == JFSX_CHACHA20P1305 && b.src_len > kCpMaxLen) return JFSX_EINVAL;
+        if (crc_mode && !b.crc) return JFSX_EINVAL;
+        if (mem == JFSX_MEM_DEVICE) {
+            // jfsx_blk's rule where an AEAD or CRC kernel touches the buffer:
+            // Open reads src, the CRC pass reads dst; the decoders and the
+            // wipe take any alignment
+            if (algo != JFSX_CIPHER_NONE && b.src_len && !aligned16(b.src)) return JFSX_EINVAL;
+            if (crc_mode && b.len && !aligned16(b.dst)) return JFSX_EINVAL;
+            if (b.dst && b.dst == b.src) return JFSX_EINVAL;  // the decoders do not run in place
+        }
+    }
+    return 0;
+}
+
+struct LoadState {
+    char *bounce = nullptr;  // pinned staging of the call's pageable images (up) and pages (down)
+    size_t bcap = 0;
+    std::vector<size_t> poff;   // host: page i at load_stage + img_bytes + poff[i], and at bounce + poff[i]
+    std::vector<char> out_b;    // host: page i comes back through the bounce buffer
+    size_t h_res = 0;           // offset of the downloaded results in load_h
+    size_t crc_off = 0;         // host CRC_GEN: offset of the CRC words behind the results
+    int zd_waves = 0;           // zstd: waves of the block-parallel decoder (0: the serial kernel)
+    bool aead = false, crc = false;
+};
+
+int load_enqueue(jfsx_ctx *c, int algo, int codec, int n, const jfsx_lblk *blks, int crc_mode, bool host,
+                 LoadState &st) {
+    hipStream_t s = c->stream;
+    const bool aead = st.aead = algo != JFSX_CIPHER_NONE;
+    const bool crc = st.crc = crc_mode == JFSX_CRC_GEN;
+    const bool zstd = codec == JFSX_CODEC_ZSTD;
+    // staging: the images, then (host) the pages
+    std::vector<size_t> ioff(n);
+    st.poff.assign(n, 0);
+    st.out_b.assign(n, 0);
+    size_t img_bytes = 0, page_bytes = 0;
+    uint64_t crc_words = 0, max_len = 0;
+    for (int i = 0; i < n; i++) {
+        ioff[i] = img_bytes;
+        img_bytes += align256(blks[i].src_len);
+        st.poff[i] = page_bytes;
+        page_bytes += align256(blks[i].len);
+        crc_words += nseg_of(blks[i].len);
+        max_len = std::max<uint64_t>(max_len, blks[i].len);
+    }
+    // device workspace of the load path
+    size_t off = 0;
+    const size_t o_lb = off; off = align256(off + sizeof(LoadBlk) * n);
+    const size_t up = off;  // the block records are uploaded from the pinned mirror
+    const size_t o_z = off; off = align256(off + sizeof(ZDev) * n);
+    const size_t o_zo = off; off = align256(off + sizeof(ZOut) * n);
+    const size_t o_res = off; off = align256(off + sizeof(LoadRes) * n);
+    const size_t o_crc = off; if (host && crc) off = align256(off + 4 * crc_words);
+    const size_t down = host && crc ? o_crc + 4 * crc_words - o_res : sizeof(LoadRes) * n;
+    const size_t o_tab = off;
+    st.h_res = up;
+    st.crc_off = o_crc - o_res;
+    int rc;
+    // every buffer of the path before the first enqueue: growing one later
+    // would free what a stage already in flight uses
+    if (zstd) {
+        st.zd_waves = zstd_decode_waves(c, n);
+        rc = ensure_zstd_decode(c, &c->load_d, &c->load_dcap, o_tab, n, &st.zd_waves);
+    } else {
+        rc = ensure_dev(c, &c->load_d, &c->load_dcap, o_tab);
+    }
+    if (rc) return rc;
+    if ((rc = ensure_host(&c->load_h, &c->load_hcap, up + down))) return rc;
+    const size_t stage_need = host ? img_bytes + page_bytes : aead ? img_bytes : 0;
+    if (stage_need && (rc = ensure_dev(c, &c->load_stage, &c->load_scap, stage_need))) return rc;
+    char *d = c->load_d, *h = c->load_h, *stage = c->load_stage;
+    // host: which images and pages go through the bounce pool (pageable caller
+    // memory; page-locked memory is copied by DMA directly).  One buffer serves
+    // both directions: the stream has finished the uploads out of it before it
+    // reaches the downloads into it.
+    std::vector<char> in_b(n, 0);
+    bool all_in = host, all_out = host, any_in = false, any_out = false;
+    if (host) {
+        for (int i = 0; i < n; i++) {
+            if (blks[i].src_len) {
+                in_b[i] = !host_pinned(blks[i].src, blks[i].src_len);
+                all_in = all_in && in_b[i];
+                any_in = any_in || in_b[i];
+            }
+            if (blks[i].len) {
+                st.out_b[i] = !host_pinned(blks[i].dst, blks[i].len);
+                all_out = all_out && st.out_b[i];
+                any_out = any_out || st.out_b[i];
+            }
+        }
+        const size_t need = std::max(any_in ? img_bytes : 0, any_out ? page_bytes : 0);
+        if (need) {
+            if (!(st.bounce = bounce_get(c, need, &st.bcap))) return JFSX_ENOMEM;
+            std::vector<std::pair<char *, const char *>> cp;
+            std::vector<size_t> cl;
+            for (int i = 0; i < n; i++)
+                if (in_b[i]) {
+                    cp.push_back({st.bounce + ioff[i], (const char *)blks[i].src});
+                    cl.push_back(blks[i].src_len);
+                    c->bounce.bytes_in += blks[i].src_len;
+                }
+            par_copy(cp, cl);
+        }
+    }
+    // block records; the Open and CRC stages' blocks
+    LoadBlk *hl = (LoadBlk *)(h + o_lb);
+    std::vector<jfsx_blk> ab(aead ? n : 0), cb(crc ? n : 0);
+    uint64_t cw = 0;
+    for (int i = 0; i < n; i++) {
+        const jfsx_lblk &b = blks[i];
+        uint8_t *img = host || aead ? (uint8_t *)(stage + ioff[i]) : (uint8_t *)b.src;
+        if (!b.src_len) img = nullptr;
+        hl[i].img = img;
+        hl[i].dst = !b.len ? nullptr : host ? (uint8_t *)(stage + img_bytes + st.poff[i]) : (uint8_t *)b.dst;
+        hl[i].crc = !crc ? nullptr : host ? (uint8_t *)(d + o_crc + 4 * cw) : b.crc;
+        hl[i].src_len = b.src_len;
+        hl[i].len = b.len;
+        cw += nseg_of(b.len);
+        if (aead) {
+            jfsx_blk &a = ab[i];
+            memset(&a, 0, sizeof(a));
+            memcpy(a.key, b.key, 32);
+            memcpy(a.nonce, b.nonce, 12);
+            memcpy(a.tag, b.tag, 16);
+            a.src = host ? img : b.src;  // host: the uploaded image is opened in place
+            a.dst = img;
+            a.len = b.src_len;
+        }
+        if (crc) {
+            jfsx_blk &k = cb[i];
+            memset(&k, 0, sizeof(k));
+            k.src = hl[i].dst;
+            k.len = b.len;
+            k.crc = hl[i].crc;
+        }
+    }
+    HIP_OK(hipMemcpyAsync(d + o_lb, h + o_lb, sizeof(LoadBlk) * n, hipMemcpyHostToDevice, s));
+    if (host) {
+        if (all_in && img_bytes) {
+            HIP_OK(hipMemcpyAsync(stage, st.bounce, img_bytes, hipMemcpyHostToDevice, s));
+        } else {
+            for (int i = 0; i < n; i++)
+                if (blks[i].src_len)
+                    HIP_OK(hipMemcpyAsync(stage + ioff[i], in_b[i] ? st.bounce + ioff[i] : (const char *)blks[i].src,
+                                          blks[i].src_len, hipMemcpyHostToDevice, s));
+        }
+    }
+    const LoadBlk *dl = (const LoadBlk *)(d + o_lb);
+    ZDev *dz = (ZDev *)(d + o_z);
+    ZOut *dzo = (ZOut *)(d + o_zo);
+    LoadRes *dres = (LoadRes *)(d + o_res);
+    // 1. Open into the staging buffer; its BlkOut[n] stays on the device
+    const BlkOut *opened = nullptr;
+    if (aead) {
+        if ((rc = enqueue_aead(c, c->load_aead, s, c->load_ev[0], c->load_ev[1], algo, true, n, ab.data(),
+                               JFSX_CRC_NONE, nullptr, nullptr, false)))
+            return rc;
+        opened = (const BlkOut *)c->load_aead.dout;
+    }
+    // 2. the gate, 3. the decoder: it sees a block only through the gate's descriptor
+    launch_begin();
+    launch_load_gate(s, n, dl, opened, dz, dzo);
+    if (zstd) launch_zstd_decompress(s, n, dz, dzo, (uint8_t *)(d + o_tab), st.zd_waves);
+    else launch_lz4_decompress(s, n, dz, dzo);
+    HIP_OK(hipGetLastError());
+    // 4. checksum() of every page, planned from len
+    if (crc && (rc = enqueue_crc(c, c->load_crc, s, c->load_ev[2], c->load_ev[3], n, cb.data(), JFSX_CRC_GEN, nullptr,
+                                 nullptr, false)))
+        return rc;
+    // 5. verdicts; pages and CRC arrays of failed blocks zeroed
+    launch_begin();
+    const int groups = (int)std::min<uint64_t>(1024, std::max<uint64_t>(1, (max_len + 65535) / 65536));
+    launch_load_finish(s, n, groups, dl, opened, dzo, zstd && st.zd_waves > 0, crc, dres);
+    HIP_OK(hipGetLastError());
+    // 6. results (and, host, the CRC words behind them) in one download; host: every page
+    HIP_OK(hipMemcpyAsync(h + st.h_res, d + o_res, down, hipMemcpyDeviceToHost, s));
+    if (host) {
+        const char *pages = stage + img_bytes;
+        if (all_out && page_bytes) {
+            HIP_OK(hipMemcpyAsync(st.bounce, pages, page_bytes, hipMemcpyDeviceToHost, s));
+        } else {
+            for (int i = 0; i < n; i++)
+                if (blks[i].len)
+                    HIP_OK(hipMemcpyAsync(st.out_b[i] ? st.bounce + st.poff[i] : (char *)blks[i].dst,
+                                          pages + st.poff[i], blks[i].len, hipMemcpyDeviceToHost, s));
+        }
+    }
+    return 0;
+}
+
+// Under c->mu for the whole call, as device batches are.
+int run_load(jfsx_ctx *c, int algo, int codec, int n, jfsx_lblk *blks, int crc_mode, int mem) {
+    int rc = check_load_args(algo, codec, n, blks, crc_mode, mem);
+    if (rc || n == 0) return rc;
+    const bool host = mem == JFSX_MEM_HOST;
+    LoadState st;
+    rc = load_enqueue(c, algo, codec, n, blks, crc_mode, host, st);
+    // the one wait of the call; after an enqueue error, nothing of it is left in flight
+    const hipError_t se = hipStreamSynchronize(c->stream);
+    for (Workspace *w : {&c->load_aead, &c->load_crc}) {
+        if (!rc && se == hipSuccess && w->timed && w->nt) {
+            hipEvent_t *ev = w == &c->load_aead ? c->load_ev : c->load_ev + 2;
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) add_kernel_ms(c, ms);
+            else (void)hipGetLastError();
+        }
+        w->n = 0;
+        w->nt = 0;
+        w->timed = false;
+        w->crc_back = false;
+    }
+    if (!rc && se != hipSuccess) {
+        note_hip_error(se, __FILE__, __LINE__, "hipStreamSynchronize(load)");
+        rc = JFSX_EIO;
+    }
+    if (!rc) {
+        const LoadRes *hr = (const LoadRes *)(c->load_h + st.h_res);
+        const char *hw = c->load_h + st.h_res + st.crc_off;
+        std::vector<std::pair<char *, const char *>> cp;
+        std::vector<size_t> cl;
+        for (int i = 0; i < n; i++) {
+            jfsx_lblk &b = blks[i];
+            b.status = hr[i].status;
+            b.out_len = hr[i].out_len;
+            b.codec_info = hr[i].codec_info;
+            if (host && st.crc) {
+                memcpy(b.crc, hw, 4 * nseg_of(b.len));
+                hw += 4 * nseg_of(b.len);
+            }
+            if (host && st.out_b[i]) {
+                cp.push_back({(char *)b.dst, st.bounce + st.poff[i]});
+                cl.push_back(b.len);
+                c->bounce.bytes_out += b.len;
+            }
+        }
+        par_copy(cp, cl);
+    }
+    if (st.bounce) bounce_put(c, st.bounce, st.bcap);
+    if (rc) return rc;
+    // jfsx_ctx_metrics: what the separate calls would have counted
+    std::lock_guard<std::mutex> g(c->stat_mu);
+    jfsx_metrics &m = c->met;
+    const bool zstd = codec == JFSX_CODEC_ZSTD;
+    uint64_t &d_blocks = zstd ? m.zstdd_blocks : m.lz4d_blocks, &d_in = zstd ? m.zstdd_in : m.lz4d_in;
+    uint64_t &d_out = zstd ? m.zstdd_out : m.lz4d_out, &d_fail = zstd ? m.zstdd_fail : m.lz4d_fail;
+    if (st.aead) m.open_batches++;
+    if (st.crc) m.crc_batches++;
+    for (int i = 0; i < n; i++) {
+        const jfsx_lblk &b = blks[i];
+        if (st.aead) {
+            m.open_blocks++;
+            m.open_bytes += b.src_len;
+            m.open_fail += b.status == JFSX_ETAG;
+        }
+        if (b.status != JFSX_ETAG) {  // the block reached the decoder
+            d_blocks++;
+            d_in += b.src_len;
+            d_out += b.out_len;
+            d_fail += b.status == JFSX_EFORMAT || b.status == JFSX_EDSTSIZE;
+            if (zstd && b.codec_info) m.zstd_serial++;
+        }
+        if (st.crc) {
+            m.crc_ranges++;
+            m.crc_bytes += b.len;
+        }
+    }
     return 0;
 }
 
@@ -1862,6 +2185,13 @@ int jfsx_ctx_open(int device, uint32_t flags, jfsx_ctx **out) {
             return JFSX_EIO;
         }
     }
+    for (hipEvent_t &e : c->load_ev) {
+        if (hipEventCreate(&e) != hipSuccess) {
+            e = nullptr;
+            jfsx_ctx_close(c);
+            return JFSX_EIO;
+        }
+    }
     for (PipeSlot &p : c->pipe) {
         if (hipEventCreateWithFlags(&p.ev_in, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&p.ev_comp, hipEventDisableTiming) != hipSuccess ||
@@ -1898,6 +2228,15 @@ int jfsx_ctx_close(jfsx_ctx *c) {
     if (c->d_tab) (void)hipFree(c->d_tab);
     if (c->rsa_d) (void)hipFree(c->rsa_d);
     if (c->rsa_h) (void)hipHostFree(c->rsa_h);
+    for (Workspace *w : {&c->load_aead, &c->load_crc}) {
+        if (w->d) (void)hipFree(w->d);
+        if (w->h) (void)hipHostFree(w->h);
+    }
+    if (c->load_d) (void)hipFree(c->load_d);
+    if (c->load_stage) (void)hipFree(c->load_stage);
+    if (c->load_h) (void)hipHostFree(c->load_h);
+    for (hipEvent_t e : c->load_ev)
+        if (e) (void)hipEventDestroy(e);
     for (auto &kv : c->bounce.idle) {
         forget_pinned(kv.second);
         (void)hipHostFree(kv.second);
@@ -2265,6 +2604,14 @@ int jfsx_zstd_compress_batch(jfsx_ctx *c, int n, jfsx_zblk *blks, int mem) {
     const int rc = run_codec(c, n, blks, mem, kZstdComp);
     if (rc == 0) tally_codec(c, c->met.zstdc_blocks, c->met.zstdc_in, c->met.zstdc_out, nullptr, n, blks);
     return rc;
+}
+
+int jfsx_load_batch(jfsx_ctx *c, int algo, int codec, int n, jfsx_lblk *blks, int crc_mode, int mem) {
+    if (!c || (n > 0 && !blks)) return JFSX_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    CtxScope es_(c);
+    HIP_OK(hipSetDevice(c->device));
+    return run_load(c, algo, codec, n, blks, crc_mode, mem);
 }
 
 int jfsx_checksum(jfsx_ctx *c, const void *data, uint64_t len, uint8_t *out) {

@@ -352,6 +352,30 @@ constexpr size_t kZcScratchStride = kZstdcScratch;
 constexpr int kZcWavesPerCu = 16;
 void launch_zstd_compress(hipStream_t s, int n, int waves, const ZDev *blks, ZOut *outs, uint8_t *scratch,
                           uint32_t *queue);
+// One-call block load (jfsx_load.hip): the kernels that chain Open, the
+// decoder and the CRC pass of jfsx_load_batch in device memory.  LoadBlk: img
+// = the bytes the decoder reads once the tag has verified (the opened image),
+// dst = the page, crc = its CRC array (device addresses; crc unused without
+// CRC_GEN).  opened = Open's BlkOut[n], null with JFSX_CIPHER_NONE.
+struct LoadBlk {
+    const uint8_t *img;
+    uint8_t *dst;
+    uint8_t *crc;
+    uint64_t src_len, len;
+};
+struct LoadRes {  // copied back to the host
+    uint64_t out_len;
+    int32_t status;
+    int32_t codec_info;
+};
+// ZDev[n] for the decoder: {img, dst, src_len, len}, or {null, null, 0, 0} for
+// a block whose tag failed; ZOut[n] initialised
+void launch_load_gate(hipStream_t s, int n, const LoadBlk *lb, const BlkOut *opened, ZDev *z, ZOut *zo);
+// the verdict of every block (jfsx_load.h) into res, then page and CRC array
+// (crc_gen) of every block that is not OK zeroed by wipe_groups workgroups;
+// use_fallback: ZOut.fallback is meaningful (the block-parallel zstd decoder ran)
+void launch_load_finish(hipStream_t s, int n, int wipe_groups, const LoadBlk *lb, const BlkOut *opened,
+                        const ZOut *zo, bool use_fallback, bool crc_gen, LoadRes *res);
 // batched RSA-OAEP unwrap (jfsx_rsa.hip): key = device jfsx_rsa::Key
 void async_detach(jfsx_ctx *c);  // jfsx_agg.cpp
 void launch_rsa_unwrap(hipStream_t s, const void *key, int n, const uint8_t *ct, uint32_t *mh, uint8_t *em,

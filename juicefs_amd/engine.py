@@ -24,6 +24,9 @@ OK, ETAG, ECRC = 0, 1, 2
 EOF = 3  # jfsx_cache_verify: short read
 EFORMAT = 4  # malformed LZ4 block / zstd frame (the library's error)
 EDSTSIZE = 5  # zstd: the output does not fit in dst_cap
+ESHORT = 6  # jfsx_load_batch: the image decoded to fewer bytes than the page ("read %s fully")
+CIPHER_NONE = -1  # jfsx_load_batch algo: the volume is not encrypted
+CODEC_LZ4, CODEC_ZSTD = 1, 2  # jfsx_load_batch codec
 EINVAL, ENODEV, EIO, ENOMEM, EMISFORMED, EAGAIN = -22, -19, -5, -12, -74, -11
 SEG = 32 << 10
 
@@ -49,6 +52,7 @@ EXPORTS = [
     "jfsx_agg_data_encrypt", "jfsx_agg_data_decrypt",
     "jfsx_data_encrypt_ex", "jfsx_data_decrypt_ex", "jfsx_agg_data_encrypt_ex", "jfsx_agg_data_decrypt_ex",
     "jfsx_file_checksum_span", "jfsx_file_checksum_batch", "jfsx_file_checksum_fold",
+    "jfsx_load_batch",
 ]
 
 
@@ -101,6 +105,15 @@ class jfsx_zblk(ctypes.Structure):
         ("src", ctypes.c_void_p), ("src_len", ctypes.c_uint64), ("dst", ctypes.c_void_p),
         ("dst_cap", ctypes.c_uint64), ("out_len", ctypes.c_uint64), ("status", ctypes.c_int32),
         ("reserved", ctypes.c_int32),
+    ]
+
+
+class jfsx_lblk(ctypes.Structure):
+    _fields_ = [
+        ("key", ctypes.c_uint8 * 32), ("nonce", ctypes.c_uint8 * 12), ("reserved", ctypes.c_uint32),
+        ("tag", ctypes.c_uint8 * 16), ("src", ctypes.c_void_p), ("src_len", ctypes.c_uint64),
+        ("dst", ctypes.c_void_p), ("len", ctypes.c_uint64), ("crc", ctypes.c_void_p),
+        ("out_len", ctypes.c_uint64), ("status", ctypes.c_int32), ("codec_info", ctypes.c_int32),
     ]
 
 
@@ -222,6 +235,7 @@ def load_library(path=LIB_PATH):
             "jfsx_zstd_compress_batch": (I, [P, I, ctypes.POINTER(jfsx_zblk), I]),
             "jfsx_agg_zstd_compress": (I, [P, ctypes.POINTER(jfsx_zblk), I]),
             "jfsx_mctx_zstd_compress_batch": (I, [P, I, ctypes.POINTER(jfsx_zblk), I]),
+            "jfsx_load_batch": (I, [P, I, I, I, ctypes.POINTER(jfsx_lblk), I, I]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -586,6 +600,52 @@ class Engine:
         # why each object went to the serial decoder (0: it did not; jfsx.h)
         self.zstd_serial_reasons = [arr[i].reserved for i in range(len(dsts))]
         return [(arr[i].status, d[:arr[i].out_len].tobytes()) for i, d in enumerate(dsts)]
+
+    # -- one-call block load (jfsx_load_batch) -----------------------------
+    @staticmethod
+    def make_lblocks(specs):
+        """specs: iterable of dicts with src, src_len, dst, len, [key, nonce, tag] (a
+        cipher), [crc] (CRC_GEN); pointers as ints."""
+        specs = list(specs)
+        arr = (jfsx_lblk * max(len(specs), 1))()
+        for i, s in enumerate(specs):
+            b = arr[i]
+            if s.get("key") is not None:
+                ctypes.memmove(b.key, bytes(s["key"]), 32)
+                ctypes.memmove(b.nonce, bytes(s["nonce"]), 12)
+                ctypes.memmove(b.tag, bytes(s["tag"]), 16)
+            b.src, b.src_len = s.get("src"), s["src_len"]
+            b.dst, b.len = s.get("dst"), s["len"]
+            b.crc = s.get("crc")
+        return arr, len(specs)
+
+    def load_batch(self, algo, codec, lblks, n, crc_mode=CRC_GEN, mem=MEM_DEVICE):
+        """cachedStore.load's Decrypt, Decompress and checksum() of n stored
+        block images in one call; per-block results in lblks[i].status
+        (OK / ETAG / EFORMAT / EDSTSIZE / ESHORT), .out_len and .codec_info."""
+        self._check(self.L.jfsx_load_batch(self.ctx, algo, codec, n, lblks, crc_mode, mem), "jfsx_load_batch")
+
+    def load(self, algo, codec, items, lengths, crc=True):
+        """Host bytes in, host bytes out.  items: the stored images -- (key,
+        nonce, C, tag) per block with a cipher, the compressed block itself with
+        CIPHER_NONE; lengths: the page length of each.  Returns (status, page,
+        crc bytes or None) per block; a block that is not OK has an all-zero
+        page and CRC array."""
+        specs, keep = [], []
+        for it, n in zip(items, lengths):
+            key, nonce, img, tag = (None, None, it, None) if algo == CIPHER_NONE else it
+            src = _u8(img)
+            page = np.empty(max(int(n), 1), np.uint8)
+            cbuf = np.empty(4 * max(1, -(-int(n) // SEG)), np.uint8)
+            keep.append((src, page, cbuf, int(n)))
+            specs.append({"key": key, "nonce": nonce, "tag": tag, "src": src.ctypes.data if src.size else None,
+                          "src_len": src.size, "dst": page.ctypes.data if n else None, "len": int(n),
+                          "crc": cbuf.ctypes.data if crc else None})
+        arr, cnt = self.make_lblocks(specs)
+        self.load_batch(algo, codec, arr, cnt, CRC_GEN if crc else CRC_NONE, MEM_HOST)
+        self.load_info = [(arr[i].out_len, arr[i].codec_info) for i in range(cnt)]
+        return [(arr[i].status, page[:n].tobytes(), cbuf.tobytes() if crc else None)
+                for i, (_, page, cbuf, n) in enumerate(keep)]
 
     # -- asynchronous batches (jfsx_*_async + jfsx_wait) ------------------
     def _ticket(self, fn, what, *args):
