@@ -158,6 +158,14 @@ int jfsx_last_error(jfsx_ctx *ctx, int *hip_error, char *msg, size_t cap);
  * 32 KiB segments with the bitsliced AES on the VALU instead of the T-table
  * AES in LDS (same bytes; a throughput trade-off). */
 #define JFSX_CTX_BITSLICE 1u
+/* AES-256-GCM's fused CRC32C in the T-table kernel: where the CRC covers the
+ * side the kernel loads (Seal over the plaintext, Open with JFSX_CRC_CT), part
+ * of its table lookups can go through the vector L1 instead of the LDS (same
+ * bytes).  JFSX_CTX_CRC_LDS: all from the LDS;
+ * JFSX_CTX_CRC_L1: the L1 path; neither: JFSX_CRC_L1=0/1 in the environment
+ * when the context opens, else the build's default.  Both: JFSX_EINVAL. */
+#define JFSX_CTX_CRC_LDS 2u
+#define JFSX_CTX_CRC_L1 4u
 int jfsx_ctx_open(int device, uint32_t flags, jfsx_ctx **out);
 int jfsx_ctx_close(jfsx_ctx *ctx);
 int jfsx_ctx_sync(jfsx_ctx *ctx);

@@ -413,6 +413,7 @@ struct jfsx_ctx {
     size_t zstd_arena_budget = 0;  // device bytes the block-parallel zstd decoder may hold (see run_codec)
     bool timing = false;
     bool bitslice = false;  // JFSX_CTX_BITSLICE
+    bool crc_l1 = false;    // crc_l1_choice, at open
     char *rsa_d = nullptr;  // batched RSA unwrap: ct | halves | em | len (device, grow-only)
     size_t rsa_dcap = 0;
     char *rsa_h = nullptr;  // pinned mirror of ct in / em + len out
@@ -821,7 +822,7 @@ int enqueue_aead(jfsx_ctx *c, Workspace &w, hipStream_t s, hipEvent_t k0, hipEve
     if (c->timing) HIP_OK(hipEventRecord(k0, s));
     if (gcm)
         launch_gcm_main(s, (int)nt, c->ncu, dq, open, crc_mode, c->bitslice, dt, db, (const GcmSched *)(d + o_sched),
-                        dpart, dpexp, c->tabs);
+                        dpart, dpexp, c->tabs, c->crc_l1);
     else
         launch_cp_main(s, (int)nt, c->ncu, dq, open, crc_mode, dt, db, (const CpSched *)(d + o_sched), dpart, dpexp,
                        c->tabs);
@@ -2126,8 +2127,21 @@ int jfsx_device_count(int *n) {
     return 0;
 }
 
+// Where the GCM kernel's fused CRC takes its data-only slice lookups: the one
+// place that decides, once per context.  The context flags win, then the
+// environment (JFSX_CRC_L1=0 / 1), then the build's default.
+static bool crc_l1_choice(uint32_t flags) {
+    if (flags & JFSX_CTX_CRC_LDS) return false;
+    if (flags & JFSX_CTX_CRC_L1) return JFSX_CRC_L1K > 0;
+    const char *e = getenv("JFSX_CRC_L1");
+    const bool on = e && *e ? atoi(e) != 0 : JFSX_CRC_L1_DEFAULT != 0;
+    return on && JFSX_CRC_L1K > 0;
+}
+
 int jfsx_ctx_open(int device, uint32_t flags, jfsx_ctx **out) {
-    if (!out || (flags & ~JFSX_CTX_BITSLICE)) return JFSX_EINVAL;
+    constexpr uint32_t known = JFSX_CTX_BITSLICE | JFSX_CTX_CRC_LDS | JFSX_CTX_CRC_L1;
+    if (!out || (flags & ~known) || (flags & (JFSX_CTX_CRC_LDS | JFSX_CTX_CRC_L1)) == (JFSX_CTX_CRC_LDS | JFSX_CTX_CRC_L1))
+        return JFSX_EINVAL;
     *out = nullptr;
     int nd = 0;
     if (hipGetDeviceCount(&nd) != hipSuccess || device < 0 || device >= nd) return JFSX_ENODEV;
@@ -2135,6 +2149,7 @@ int jfsx_ctx_open(int device, uint32_t flags, jfsx_ctx **out) {
     jfsx_ctx *c = new jfsx_ctx();
     c->device = device;
     c->bitslice = (flags & JFSX_CTX_BITSLICE) != 0;
+    c->crc_l1 = crc_l1_choice(flags);
     (void)jfsx_device_numa_node(device, &c->numa_node);
     int ncu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0)

@@ -59,6 +59,66 @@ __device__ __forceinline__ uint32_t crc_piece(const char *lds, uint32_t A, uint3
 #undef X3
 }
 
+// The A-independent slice lookups through the vector L1.  Tables 4..15 of a
+// piece's step are indexed by the data words p1..p3 alone, so where the data
+// is in registers long before the step (the two-row loop of gcm_main with the
+// CRC over the loaded side) K of them, tables 4 .. 3 + K, are gathered from the
+// device image of the tables (DevTables::crc) instead of its LDS copy: issued
+// early, XOR-folded as they return, and handed to crc_piece_l1 as L.  A lookup
+// is one address op and one global_load_dword (SGPR base, the table's offset
+// in the instruction); it takes no LDS cycle.
+typedef __attribute__((address_space(1))) const uint32_t gcu32;
+// term i (0 .. K - 1) of a piece: table 4 + i at byte i & 3 of p[1 + i / 4]
+// Two bases inside the table image, each an SGPR pair the compiler cannot fold
+// back into one (it would then add the tables' offsets on the VALU, 64 bits
+// wide): tables 4..11 are within the instruction's signed 13-bit offset of the
+// first, tables 12..15 of the second.
+struct CrcL1Base {
+    uint64_t a, b;  // image + 8192, image + 12288
+};
+__device__ __forceinline__ CrcL1Base crc_l1_base(const uint32_t *gcrc) {
+    CrcL1Base g = {(uint64_t)gcrc + 8192u, (uint64_t)gcrc + 12288u};
+    asm volatile("" : "+s"(g.a), "+s"(g.b));
+    return g;
+}
+// term I (0 .. K - 1) of a piece: table 4 + I at byte I & 3 of p[1 + I / 4]
+template <int I>
+__device__ __forceinline__ uint32_t crc_l1_term(const CrcL1Base &g, uint4 p) {
+    const uint32_t w = I < 4 ? p.y : (I < 8 ? p.z : p.w);
+#if JFSX_CRCSDWA
+    const uint32_t o = byte_x4<(I & 3)>(w);
+#else
+    const uint32_t o = ((w >> (8 * (I & 3))) & 0xffu) << 2;
+#endif
+    const __attribute__((address_space(1))) char *t = (const __attribute__((address_space(1))) char *)(I < 8 ? g.a : g.b);
+    return *(gcu32 *)(t + o + (1024 * (4 + I) - (I < 8 ? 8192 : 12288)));
+}
+
+// group S of the UR rows' gathers: terms LG (S / UR) .. + LG - 1 of row S % UR
+template <int S, int LG, int UR, int J = 0>
+__device__ __forceinline__ void crc_l1_issue(const CrcL1Base &g, const uint4 (&d)[UR], uint32_t (&lv)[LG]) {
+    if constexpr (J < LG) {
+        lv[J] = crc_l1_term<LG * (S / UR) + J>(g, d[S % UR]);
+        crc_l1_issue<S, LG, UR, J + 1>(g, d, lv);
+    }
+}
+
+// crc_piece with the lookups of tables 4 .. 3 + K (K = 4, 8 or 12) already
+// summed in L
+template <uint32_t CB, int K, int S = 16>
+__device__ __forceinline__ uint32_t crc_piece_l1(const char *lds, uint32_t A, uint32_t p0, uint32_t p1, uint32_t p2,
+                                                 uint32_t p3, uint32_t L) {
+    static_assert(K == 4 || K == 8 || K == 12, "whole data words only");
+#define X3(a, b, c) __builtin_amdgcn_bitop3_b32((a), (b), (c), 0x96)
+    uint32_t s = S < 0 ? A : X3(CRC_T(S, A, 0), CRC_T(S + 1, A, 1), CRC_T(S + 2, A, 2)) ^ CRC_T(S + 3, A, 3);
+    uint32_t q = p0 ^ s;
+    uint32_t r = X3(X3(CRC_T(0, q, 0), CRC_T(1, q, 1), CRC_T(2, q, 2)), CRC_T(3, q, 3), L);
+    if constexpr (K < 8) r = X3(r, X3(CRC_T(8, p2, 0), CRC_T(9, p2, 1), CRC_T(10, p2, 2)), CRC_T(11, p2, 3));
+    if constexpr (K < 12) r = X3(X3(r, CRC_T(12, p3, 0), CRC_T(13, p3, 1)), CRC_T(14, p3, 2), CRC_T(15, p3, 3));
+#undef X3
+    return r;
+}
+
 // byte-serial tail: crc_raw(shift(A,1008), first n bytes of the piece)
 // CRCMODE bit 2 (JFSX_CRC_CT): the segment CRCs cover the ciphertext side
 // (object checksum, pkg/object/checksum.go:31-53) instead of the plaintext

@@ -175,11 +175,23 @@ __device__ __forceinline__ void aes_r2_uniform(const char *lds, uint32_t loff, c
 
 // aes_ctr_blocks with rounds 1-2 taken from the lane's counter-uniform terms u;
 // ks comes out without the last round key (rk[56..59]).
-template <int NS>
+// side(AesStep<i>) runs after the i-th of the 12 round groups (rounds 1-2, then
+// 3 .. 13): the caller's place for work that fills the rounds' latency (the
+// CRC's L1 gathers); AesNoSide does nothing there.
+template <int I>
+struct AesStep {
+    static constexpr int value = I;
+};
+struct AesNoSide {
+    template <int I>
+    __device__ __forceinline__ void operator()(AesStep<I>) const {}
+};
+template <int NS, class Side = AesNoSide>
 __device__ __forceinline__ void aes_ctr_blocks_u(const char *lds, uint32_t loff, const uint32_t *rk,
                                                  const uint32_t *k1, const uint32_t (&ctr)[NS],
                                                  const uint32_t (&u)[NS][4], const uint32_t (&du)[NS][4],
-                                                 const uint32_t (&cym)[NS], uint32_t (&ks)[NS][4]) {
+                                                 const uint32_t (&cym)[NS], uint32_t (&ks)[NS][4],
+                                                 const Side &side = Side()) {
     uint32_t a[NS][4], b[NS][4];
     // u, du wave-uniform (SGPR operands); carry lanes (cym = ~0) add du = u(U) ^ u(U + 1)
 #define UC(t, w) (__builtin_amdgcn_bitop3_b32((t), cym[s], du[s][w], 0x78) ^ u[s][w]) /* t ^ (cym & du) ^ u */
@@ -193,15 +205,25 @@ __device__ __forceinline__ void aes_ctr_blocks_u(const char *lds, uint32_t loff,
         b[s][3] = UC(rotl8(TA(a0, 1)), 3);
     }
 #undef UC
+    side(AesStep<0>());
 #pragma unroll
     for (int s = 0; s < NS; s++) { AES_ROUND(a[s][0], a[s][1], a[s][2], a[s][3], b[s][0], b[s][1], b[s][2], b[s][3], 3); }
-#pragma unroll
-    for (int r = 4; r <= 13; r += 2) {
-#pragma unroll
-        for (int s = 0; s < NS; s++) { AES_ROUND(b[s][0], b[s][1], b[s][2], b[s][3], a[s][0], a[s][1], a[s][2], a[s][3], r); }
-#pragma unroll
-        for (int s = 0; s < NS; s++) { AES_ROUND(a[s][0], a[s][1], a[s][2], a[s][3], b[s][0], b[s][1], b[s][2], b[s][3], r + 1); }
-    }
+    side(AesStep<1>());
+#define JFSX_AES_PAIR(r)                                                                                                \
+    _Pragma("unroll") for (int s = 0; s < NS; s++) {                                                                    \
+        AES_ROUND(b[s][0], b[s][1], b[s][2], b[s][3], a[s][0], a[s][1], a[s][2], a[s][3], r);                           \
+    }                                                                                                                   \
+    side(AesStep<(r) - 2>());                                                                                           \
+    _Pragma("unroll") for (int s = 0; s < NS; s++) {                                                                    \
+        AES_ROUND(a[s][0], a[s][1], a[s][2], a[s][3], b[s][0], b[s][1], b[s][2], b[s][3], (r) + 1);                     \
+    }                                                                                                                   \
+    side(AesStep<(r) - 1>());
+    JFSX_AES_PAIR(4)
+    JFSX_AES_PAIR(6)
+    JFSX_AES_PAIR(8)
+    JFSX_AES_PAIR(10)
+    JFSX_AES_PAIR(12)
+#undef JFSX_AES_PAIR
 #pragma unroll
     for (int s = 0; s < NS; s++) {
         // the last round key is left out: the caller folds it into the data XOR
@@ -487,7 +509,11 @@ __device__ uint64_t g_wgtrace[4 * 65536];
 // One task (a block's <= 4 MiB byte range) on the whole workgroup.  The AES
 // and CRC tables are already in LDS; the GHASH table of the task's key is
 // built here.  Every thread of the workgroup calls this.
-template <bool OPEN, int CRCMODE, int NS, int BS>
+// KL1: in the two-row loop, K of the CRC step's data-only slice lookups come
+// from the vector L1 instead of the LDS (crc_piece_l1; 0: all from the LDS).
+// Only where the CRC covers the loaded side, so the gathers can be issued
+// inside the AES rounds, long before the step that needs them.
+template <bool OPEN, int CRCMODE, int NS, int BS, int KL1>
 __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDev *__restrict__ blks,
                                          const GcmSched *__restrict__ sched, uint32_t *__restrict__ partial,
                                          uint32_t *__restrict__ pexp, const DevTables &tab, uint32_t tid,
@@ -666,6 +692,9 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
     // shape has twice the VGPRs and takes JFSX_HYB_UR): the UR AES chains
     // interleave, GHASH/CRC stay sequential (register peak of one row)
     constexpr int UR = BS == 2 ? JFSX_HYB_UR : JFSX_UR0;
+    // the CRC's input is the loaded row itself: the plaintext in Seal, the
+    // ciphertext (JFSX_CRC_CT) in Open
+    constexpr bool kL1 = KL1 > 0 && kRowSplit && JFSX_UCTR && CRCMODE != 0 && OPEN == ((CRCMODE & 4) != 0);
     if (NS == 1 && act[0] && rf >= r0 + UR) {
         uint4 nn[UR];
 #pragma unroll
@@ -689,15 +718,55 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
         uint4 pc[UR], pq[UR];
         bool pend = false;
         uint32_t pr0 = 0;
+        const CrcL1Base l1g = kL1 ? crc_l1_base(tab.crc) : CrcL1Base{0, 0};
         for (; r0 + UR - 1 < rf; r0 += UR) {
             uint4 dd[UR];
 #pragma unroll
             for (int u = 0; u < UR; u++) dd[u] = nn[u];
             const uint64_t o0 = ld0[0] + 1024 * r0 + lo;
-            if (r0 + 2 * UR - 1 < rf) {
+            // (the L1 path prefetches after its last gather group, below: the
+            // returns come in order, and a fold must not wait for HBM)
+            if (!kL1 && r0 + 2 * UR - 1 < rf) {
 #pragma unroll
                 for (int u = 0; u < UR; u++) nn[u] = ald16(src + o0 + 1024 * (UR + u));
             }
+            // UR * KL1 gathers in groups of LG terms of one row, one group per
+            // AES round group; a group is folded into its row's crcL LLAG round
+            // groups after its issue, so LLAG * LG values are in flight and
+            // the rounds between hide the L1.  The prefetch follows the last
+            // group.  The full scheduling barriers keep each group in its
+            // place (an AES round needs all of the round before, so there is
+            // little to reorder across them).
+            constexpr int LG = kL1 ? JFSX_CRC_L1LG : 1, LLAG = JFSX_CRC_L1LAG, LSTEPS = kL1 ? UR * KL1 / LG : 0;
+            static_assert(!kL1 || (KL1 % LG == 0 && LSTEPS + LLAG <= 12),
+                          "the gathers, their folds and the prefetch must fit the 12 round groups");
+            uint32_t crcL[UR], lv[LSTEPS ? LSTEPS : 1][LG];
+#pragma unroll
+            for (int u = 0; u < UR; u++) crcL[u] = 0;
+            const bool pre = r0 + 2 * UR - 1 < rf;
+            auto side = [&](auto step) {
+                if constexpr (kL1) {
+                    constexpr int S = decltype(step)::value;
+                    __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (S >= LLAG && S - LLAG < LSTEPS) {
+                        constexpr int F = S - LLAG;  // group F has returned
+                        uint32_t t = crcL[F % UR];
+#pragma unroll
+                        for (int j = 0; j + 1 < LG; j += 2) t = xor3(t, lv[F][j], lv[F][j + 1]);
+                        if (LG & 1) t ^= lv[F][LG - 1];
+                        crcL[F % UR] = t;
+                    }
+                    if constexpr (S < LSTEPS) {
+                        crc_l1_issue<S, LG, UR>(l1g, dd, lv[S]);
+                    } else if constexpr (S == LSTEPS) {
+                        if (pre) {
+#pragma unroll
+                            for (int u = 0; u < UR; u++) nn[u] = ald16(src + o0 + 1024 * (UR + u));
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            };
             if (SWP && pend) {
 #pragma unroll
                 for (int u = 0; u < UR; u++) {
@@ -735,7 +804,7 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
                         d2[u][k] = u2[u][k] ^ __builtin_amdgcn_readlane(uw[k], i0 + 1);
                     }
                 }
-                aes_ctr_blocks_u<UR>(lds, loff, rk, k1, ctrs, u2, d2, cym, ks2);
+                aes_ctr_blocks_u<UR>(lds, loff, rk, k1, ctrs, u2, d2, cym, ks2, side);
             }
 #else
             aes_ctr_blocks<UR>(lds, loff, rk, k1, ctrs, ks2);
@@ -762,7 +831,10 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
 #ifndef JFSX_ABLATE_GHASH
                 ghash_step(lds, st[0].acc, gl, c);
 #endif
-                if (CRCMODE) st[0].A = crc_piece<kLdsCrc>(lds, st[0].A, cq.x, cq.y, cq.z, cq.w);
+                if constexpr (kL1)
+                    st[0].A = crc_piece_l1<kLdsCrc, (kL1 ? KL1 : 4)>(lds, st[0].A, cq.x, cq.y, cq.z, cq.w, crcL[u]);
+                else if (CRCMODE)
+                    st[0].A = crc_piece<kLdsCrc>(lds, st[0].A, cq.x, cq.y, cq.z, cq.w);
                 if (CRCMODE && ((rb0 + (uint32_t)r0 + u) & 31) == 31) {
                     crc_segment_done<CRCMODE>(blk, tab, lane, xl, st[0].seg0, st[0].A, st[0].seg0 < st[0].sub0, lds,
                                               c0);
@@ -939,7 +1011,7 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
 // dispatched in order, round-robin over the XCDs, and the next one waits for
 // a CU of its own XCD (measured with the TRACE variant on configs[4]'s
 // 64 KiB-4 MiB blocks: CUs 79 % busy, 115 us mean gap between tasks).
-template <bool OPEN, int CRCMODE, int NS, int BS>
+template <bool OPEN, int CRCMODE, int NS, int BS, int KL1 = 0>
 __global__ __launch_bounds__(GcmShape<BS>::threads) void gcm_main_k(const Task *__restrict__ tasks, uint32_t ntasks,
                                                        uint32_t *__restrict__ queue,
                                                        const BlkDev *__restrict__ blks,
@@ -991,7 +1063,7 @@ __global__ __launch_bounds__(GcmShape<BS>::threads) void gcm_main_k(const Task *
         if (ti >= ntasks) break;  // the same for every wave: the queue is exhausted
         __syncthreads();          // every wave holds ti: s_task may take the next index
         if (tid == 0) s_task = atomicAdd(queue, 1u);  // the next task's index arrives during this one
-        gcm_task<OPEN, CRCMODE, NS, BS>(lds, tasks[ti], blks, sched, partial, pexp, tab, tid, wave, lane, loff, gl,
+        gcm_task<OPEN, CRCMODE, NS, BS, KL1>(lds, tasks[ti], blks, sched, partial, pexp, tab, tid, wave, lane, loff, gl,
                                         xl, hyb);
     }
 }
@@ -1448,9 +1520,12 @@ void launch_gcm_keysetup(hipStream_t s, int n, const KeyIn *keys, const BlkDev *
                            (int)(bitslice || hybrid));
 }
 
+// crc_l1: the 16-wave T-table kernel takes JFSX_CRC_L1K of the fused CRC's
+// slice lookups through the vector L1 where the CRC covers the loaded side
+// (gcm_task's KL1); false, or any other shape or mode: every lookup from the LDS
 void launch_gcm_main(hipStream_t s, int ntasks, int ncu, uint32_t *queue, bool open, int crc_mode, bool bitslice,
                      const Task *tasks, const BlkDev *blks, const GcmSched *sched, uint32_t *partial, uint32_t *pexp,
-                     DevTables t) {
+                     DevTables t, bool crc_l1) {
     if (ntasks <= 0) return;
     const unsigned grid = (unsigned)(ntasks < ncu ? ntasks : ncu);  // persistent: one workgroup per CU
     // queue: zeroed by the caller (uploaded with the batch descriptors)
@@ -1470,6 +1545,10 @@ void launch_gcm_main(hipStream_t s, int ntasks, int ncu, uint32_t *queue, bool o
         else if (hyb != 0xffffffffu)                                                                         \
             hipLaunchKernelGGL((gcm_main_k<O, C, 1, 2>), dim3(grid), dim3(GcmShape<2>::threads), 0, s, tasks,    \
                                (uint32_t)ntasks, queue, blks, sched, partial, pexp, t, hyb);                 \
+        else if (crc_l1 && (C) != 0 && (O) == (((C) & 4) != 0))                                              \
+            hipLaunchKernelGGL((gcm_main_k<O, C, kStreams, 0, ((C) != 0 && (O) == (((C) & 4) != 0)) ? JFSX_CRC_L1K : 0>), \
+                               dim3(grid), dim3(GcmShape<0>::threads), 0, s, tasks, (uint32_t)ntasks, queue, blks,  \
+                               sched, partial, pexp, t, 0u);                                                 \
         else                                                                                                 \
             hipLaunchKernelGGL((gcm_main_k<O, C, kStreams, 0>), dim3(grid), dim3(GcmShape<0>::threads), 0, s,    \
                                tasks, (uint32_t)ntasks, queue, blks, sched, partial, pexp, t, 0u);           \

@@ -65,6 +65,23 @@ constexpr int kThreads = kWaves * 64;
 #ifndef JFSX_CRCSDWA
 #define JFSX_CRCSDWA 1
 #endif
+// Fused CRC in the 16-wave GCM kernel: K of the step's 12 data-only slice
+// lookups through the vector L1 (4, 8 or 12; crc_piece_l1, jfsx_dev.h), issued
+// inside the AES rounds in groups of LG and folded LAG round groups later
+// (gcm_task; DESIGN 4.1, round 7, has the measurements behind 12 / 4 / 3), and
+// whether a context takes that path unless told otherwise (crc_l1_choice).
+#ifndef JFSX_CRC_L1K
+#define JFSX_CRC_L1K 12
+#endif
+#ifndef JFSX_CRC_L1LG
+#define JFSX_CRC_L1LG 4
+#endif
+#ifndef JFSX_CRC_L1LAG
+#define JFSX_CRC_L1LAG 3
+#endif
+#ifndef JFSX_CRC_L1_DEFAULT
+#define JFSX_CRC_L1_DEFAULT 1
+#endif
 // T-table rounds 2..13 with pre-rotated round keys folded into a v_bitop3 (AES_COL).
 #ifndef JFSX_RKR
 #define JFSX_RKR 1
@@ -303,7 +320,7 @@ void launch_gcm_keysetup(hipStream_t s, int n, const KeyIn *keys, const BlkDev *
 // persistent over min(ntasks, ncu) workgroups; queue: 4 device bytes the caller zeroed (enqueue_aead uploads it)
 void launch_gcm_main(hipStream_t s, int ntasks, int ncu, uint32_t *queue, bool open, int crc_mode, bool bitslice,
                      const Task *tasks, const BlkDev *blks, const GcmSched *sched, uint32_t *partial, uint32_t *pexp,
-                     DevTables t);
+                     DevTables t, bool crc_l1);
 // max_slots: the most partial slots any block of the batch has (sizes the workgroup)
 void launch_gcm_finalize(hipStream_t s, int n, bool open, int crc_mode, const BlkDev *blks, const GcmSched *sched,
                          const uint32_t *partial, const uint32_t *pexp, BlkOut *out, uint32_t max_slots);

@@ -19,6 +19,8 @@ CRC_NONE, CRC_GEN, CRC_VERIFY = 0, 1, 2
 CRC_CT = 4  # flag: segment CRCs over the ciphertext (object checksum)
 CRC_BOTH = 8  # flag (with CRC_GEN): plaintext CRCs, then ciphertext CRCs, in one array
 CTX_BITSLICE = 1  # context flag: AES-GCM keystream from the bitsliced AES (VALU)
+CTX_CRC_LDS = 2  # context flag: the GCM kernel's fused CRC looks up in the LDS only
+CTX_CRC_L1 = 4  # context flag: part of those lookups through the vector L1 (neither: JFSX_CRC_L1, else the default)
 MEM_DEVICE, MEM_HOST = 0, 1
 OK, ETAG, ECRC = 0, 1, 2
 EOF = 3  # jfsx_cache_verify: short read
@@ -407,7 +409,8 @@ class Engine:
     """One GPU context (device ordinal + HIP stream + workspace)."""
 
     def __init__(self, device=0, flags=0):
-        """flags: 0 or CTX_BITSLICE (AES-GCM keystream from the bitsliced AES)."""
+        """flags: 0 or CTX_BITSLICE (AES-GCM keystream from the bitsliced AES),
+        optionally with one of CTX_CRC_LDS / CTX_CRC_L1 (the GCM kernel's CRC lookups)."""
         self.L = load_library()
         if device_count() <= device:
             raise RuntimeError("jfsx: no HIP device %d visible (the engine has no CPU path)" % device)
