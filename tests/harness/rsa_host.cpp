@@ -1,5 +1,6 @@
 // CPU build of juicefs_amd/csrc/jfsx_rsa.h (test infrastructure only): the
-// RSA-OAEP unwrap arithmetic, checked by tests/test_rsa.py against libcrypto.
+// RSA-OAEP unwrap arithmetic, checked by tests/test_rsa.py against libcrypto
+// and against the big-integer model of tests/rsa_model.py.
 #include <stdint.h>
 #include <string.h>
 
@@ -42,6 +43,18 @@ uint64_t rsa_exp_trace(const uint8_t *m_be, const uint8_t *e_be, const uint8_t *
     to_be(r, kLimbs, out_be, 4 * kLimbs);
     *ops = g_ops;
     return g_trace;
+}
+
+// c mod m by the unwrap's input reduction (reduce_2048): c 256 bytes, m an odd
+// 1024-bit number, out 128 bytes, all big-endian
+void rsa_reduce(const uint8_t *m_be, const uint8_t *c_be, uint8_t *out_be) {
+    using namespace jfsx_rsa;
+    uint32_t m[kLimbs], c[2 * kLimbs], r2[kLimbs], r[kLimbs];
+    from_be(m_be, 4 * kLimbs, m, kLimbs);
+    from_be(c_be, kModBytes, c, 2 * kLimbs);
+    mont_r2(m, r2);
+    reduce_2048(c, m, mont_inv32(m[0]), r2, r);
+    to_be(r, kLimbs, out_be, 4 * kLimbs);
 }
 
 // mod_exp28_pair's lane exchange on the CPU: the two lanes are two threads

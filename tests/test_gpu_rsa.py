@@ -20,8 +20,11 @@ def eng():
 
 
 @pytest.fixture(scope="module")
-def rsae():
-    return enc.NewRSAEncryptor(enc.GenerateRsaKey(2048))
+def rsae(eng):
+    r = enc.NewRSAEncryptor(enc.GenerateRsaKey(2048))
+    # DecryptBatch unwraps on the host when the engine refuses the key: not here
+    assert r._device_key(eng) is not None
+    return r
 
 
 def test_batch_unwrap_matches_libcrypto(eng, rsae):

@@ -2,7 +2,9 @@
 Montgomery CRT exponentiation, SHA-256/MGF1 and EME-OAEP decoding, compiled
 for the host (tests/harness/rsa_host.cpp) and checked against libcrypto's
 RSA-OAEP(SHA-256, label "keys") -- the rsaEncryptor of
-pkg/object/encrypt.go:124-134 -- on freshly generated 2048-bit keys."""
+pkg/object/encrypt.go:124-134 -- on freshly generated 2048-bit keys, and
+against the big-integer model of tests/rsa_model.py on the fixed keys of
+tests/golden/rsa_keys.json."""
 import ctypes
 import hashlib
 import os
@@ -11,6 +13,7 @@ import subprocess
 import pytest
 
 from juicefs_amd import encrypt as enc
+from tests import rsa_model as M
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -136,26 +139,6 @@ def test_pair_exponentiation_matches_pow_with_one_trace(rsa, keypair):
         assert nops == 8 + 342 * 4 + 1 + 342 * 8
 
 
-def _oaep_encode(msg, seed, label=b"keys", k=256, db_patch=None):
-    import hashlib as h
-    lh = h.sha256(label).digest()
-    ps = b"\0" * (k - len(msg) - 2 * 32 - 2)
-    db = bytearray(lh + ps + b"\x01" + msg)
-    if db_patch:
-        db_patch(db)
-
-    def mgf(s, n):
-        out = b""
-        c = 0
-        while len(out) < n:
-            out += h.sha256(s + c.to_bytes(4, "big")).digest()
-            c += 1
-        return out[:n]
-    mdb = bytes(a ^ b for a, b in zip(db, mgf(seed, len(db))))
-    ms = bytes(a ^ b for a, b in zip(seed, mgf(mdb, 32)))
-    return bytearray(b"\0" + ms + mdb)
-
-
 def test_oaep_decode_checks_without_branching_on_the_data(rsa):
     """The decode's outcomes, each reached by the masked scan (RFC 8017
     7.1.2 step 3g, Go's decryptOAEP): good messages of every length decode;
@@ -164,17 +147,161 @@ def test_oaep_decode_checks_without_branching_on_the_data(rsa):
     seed = os.urandom(32)
     for n in (0, 1, 32, 190):
         m = os.urandom(n)
-        em = _oaep_encode(m, seed)
+        em = M.oaep_encode(m, seed)
         buf = ctypes.create_string_buffer(bytes(em), 256)
         assert rsa.oaep(buf, b"keys", 4) == n and buf.raw[:n] == m
     bad = []
-    em = _oaep_encode(b"k" * 32, seed)
+    em = M.oaep_encode(b"k" * 32, seed)
     em[0] = 1
     bad.append(em)
-    bad.append(_oaep_encode(b"k" * 32, seed, label=b"other"))
-    bad.append(_oaep_encode(b"", seed, db_patch=lambda db: db.__setitem__(len(db) - 1, 0)))  # no 0x01 at all
-    bad.append(_oaep_encode(b"k" * 32, seed, db_patch=lambda db: db.__setitem__(40, 7)))  # junk in the padding
-    bad.append(_oaep_encode(b"k" * 32, seed, db_patch=lambda db: db.__setitem__(40, 2)))
+    bad.append(M.oaep_encode(b"k" * 32, seed, label=b"other"))
+    bad.append(M.oaep_encode(b"", seed, patch=lambda db: db.__setitem__(len(db) - 1, 0)))  # no 0x01 at all
+    bad.append(M.oaep_encode(b"k" * 32, seed, patch=lambda db: db.__setitem__(40, 7)))  # junk in the padding
+    bad.append(M.oaep_encode(b"k" * 32, seed, patch=lambda db: db.__setitem__(40, 2)))
     for em in bad:
         buf = ctypes.create_string_buffer(bytes(em), 256)
         assert rsa.oaep(buf, b"keys", 4) == -1
+
+
+# ---------------------------------------------------------------------------
+# the big-integer model (tests/rsa_model.py) and the fixed keys
+# (tests/golden/rsa_keys.json): reproducible, q > p as well as p > q, primes at
+# the edges of the 1024-bit range
+# ---------------------------------------------------------------------------
+FIXED = list(M.fixed_keys())
+NOPS = 8 + 342 * 4 + 1 + 342 * 8  # the one trace of mod_exp28 (pinned above)
+
+
+def test_fixed_keys_are_what_their_names_say():
+    ks = M.fixed_keys()
+    T, B = 1 << 1024, 1 << 1023
+    assert (ks["top"].p, ks["top"].q) == (T - 105, T - 179) == (ks["top_swapped"].q, ks["top_swapped"].p)
+    assert (ks["bottom"].p, ks["bottom"].q) == (B + 1493, B + 1155)
+    wq, wp = ks["wide_q_gt_p"], ks["wide_p_gt_q"]
+    assert (wq.p, wq.q) == (B + 1155, T - 105) == (wp.q, wp.p)
+    assert ks["plain_q_gt_p"].p < ks["plain_q_gt_p"].q and ks["plain_p_gt_q"].p > ks["plain_p_gt_q"].q
+    assert 0 < T - (1 << 200) - ks["holes"].p < 1 << 16 and 0 < ks["holes"].q - B - (1 << 500) < 1 << 16
+    for name, k in ks.items():
+        for m in (k.p, k.q):  # shape only; tests/golden/make_rsa_keys.py proves primality
+            assert m.bit_length() == 1024 and pow(2, m - 1, m) == 1, name
+        assert k.d * M.E % (k.p - 1) == 1 and k.qinv * k.q % k.p == 1
+
+
+def test_model_refuses_a_prime_where_e_is_not_invertible():
+    with pytest.raises(ValueError):
+        M.key(2 * M.E + 1, M.fixed_keys()["top"].q)  # gcd(e, p - 1) = e; never reaches a primality question
+
+
+def test_model_against_libcrypto_both_ways(keypair):
+    """The model against an implementation we did not write: libcrypto's
+    ciphertexts decrypt in the model, the model's in libcrypto, and a
+    model-made bad encoding is libcrypto's decryption error."""
+    _, rsae, comps = keypair
+    p, q, dp, dq, qinv = (int.from_bytes(c, "big") for c in comps)
+    k = M.key(p, q)
+    assert (k.dp, k.dq, k.qinv) == (dp, dq, qinv)
+    assert M.components(k) == tuple(comps)
+    for i, n in enumerate((0, 1, 31, 32, 33, 190)):
+        m = M.det_bytes(n, "libcrypto", n)
+        assert M.decrypt(k, rsae.Encrypt(m)) == m
+        ct = M.ct256(M.encrypt_em(k, M.oaep_encode(m, M.det_bytes(32, "libcrypto seed", i))))
+        assert rsae.Decrypt(ct) == m
+    bad = [M.oaep_encode(b"k" * 32, bytes(32), label=b"other"),
+           M.oaep_encode(b"", bytes(32), patch=lambda db: db.__setitem__(len(db) - 1, 0)),
+           M.oaep_encode(b"k" * 32, bytes(32), patch=lambda db: db.__setitem__(40, 2))]
+    for em in bad:
+        ct = M.ct256(M.encrypt_em(k, em))
+        assert M.decrypt(k, ct) is None
+        with pytest.raises(enc.EncryptError):
+            rsae.Decrypt(ct)
+    assert M.decrypt(k, M.ct256(k.n)) is None and M.decrypt(k, b"\0" * 257) is None
+
+
+@pytest.mark.parametrize("name", FIXED)
+def test_case_set_reaches_the_paths_it_is_for(name):
+    M.assert_reaches_paths(name)
+
+
+@pytest.mark.parametrize("name", FIXED)
+def test_unwrap_fixed_key_matches_model(rsa, name):
+    """The host build of jfsx_rsa.h on the whole ciphertext set of one fixed
+    key (the set the GPU test submits), item by item against the model.  The
+    rule for a ciphertext longer than the modulus lives in the C-ABI
+    (jfsx_api.cpp), not in the header; test_gpu_rsa_fixed.py covers it."""
+    M.assert_reaches_paths(name)
+    k = M.fixed_keys()[name]
+    comps = M.components(k)
+    for label, cases in ((b"keys", M.case_set(name)), (b"", M.empty_label_case_set(name))):
+        for c in cases:
+            if len(c.ct) <= 256:
+                assert unwrap(rsa, comps, c.ct, label=label) == c.expect, (name, c.name)
+
+
+def _distinct_primes():
+    seen = {}
+    for name, k in M.fixed_keys().items():
+        seen.setdefault(k.p, name + ".p")
+        seen.setdefault(k.q, name + ".q")
+    return sorted((nm, m) for m, nm in seen.items())
+
+
+def test_input_reduction_on_the_fixed_primes(rsa):
+    """reduce_2048 itself, c mod p and c mod q for every fixed key: the valid
+    ciphertexts and the edges of the 2048-bit range, with none, one and both
+    of its corrections due (by the model's count).  The exponentiation's
+    28-bit limbs leave room for an input in [m, 2m), so a lost second
+    correction does not show in an unwrap's result; it shows here."""
+    R = M.R
+    seen = set()
+    for name, k in M.fixed_keys().items():
+        for m in (k.p, k.q):
+            cs = [c for _, _, c in M.valid_ints(name)]
+            cs += [0, 1, m - 1, m, m + 1, 2 * m, 2 * m - 1, R - 1, R, R + 1, (R - 1) * R, R * R - 1, k.n - 1, k.n,
+                   R * R - m, (R * R - 1) // m * m, (R * R - 1) // m * m - 1]
+            mb = m.to_bytes(128, "big")
+            for c in cs:
+                out = ctypes.create_string_buffer(128)
+                rsa.rsa_reduce(mb, c.to_bytes(256, "big"), out)
+                ncorr = M.reduce_corrections(m, c)
+                assert int.from_bytes(out.raw, "big") == c % m, (name, hex(m), hex(c), ncorr)
+                seen.add((name, m == k.p, ncorr))
+    assert {n for _, _, n in seen} == {0, 1, 2}
+    assert ("bottom", True, 2) in seen and ("bottom", False, 2) in seen
+
+
+def test_exponentiation_on_the_fixed_primes(rsa, keypair):
+    """mod_exp28 on every fixed prime: edge bases and edge exponents equal
+    pow(), with the one operation trace, the same as a generated key's."""
+    rsa.rsa_exp_trace.restype = ctypes.c_uint64
+    traces = set()
+    for nm, m in [("generated.p", int.from_bytes(keypair[2][0], "big"))] + _distinct_primes():
+        mb = m.to_bytes(128, "big")
+        for e in (pow(M.E, -1, m - 1), 0, 1, (1 << 1024) - 1):
+            for x in (0, 1, 2, m - 1, m - 2, (1 << 1023) - 1):
+                assert x < m
+                out = ctypes.create_string_buffer(128)
+                ops = ctypes.c_uint64()
+                h = rsa.rsa_exp_trace(mb, e.to_bytes(128, "big"), x.to_bytes(128, "big"), out, ctypes.byref(ops))
+                assert int.from_bytes(out.raw, "big") == pow(x, e, m), (nm, hex(x), hex(e))
+                traces.add((h, ops.value))
+    assert len(traces) == 1 and next(iter(traces))[1] == NOPS, traces
+
+
+def test_pair_exponentiation_on_the_fixed_primes(rsa):
+    """mod_exp28_pair (two threads in lock step) on every fixed prime, four
+    (base, exponent) edges each: 40 calls, each a fifth of a second."""
+    rsa.rsa_exp_pair_trace.restype = ctypes.c_uint64
+    traces = set()
+    primes = _distinct_primes()
+    assert len(primes) == 10
+    for nm, m in primes:
+        d = pow(M.E, -1, m - 1)
+        for x, e in ((m - 1, d), ((1 << 1023) - 1, (1 << 1024) - 1), (2, d), (m - 2, 1)):
+            out = ctypes.create_string_buffer(128)
+            ops, same = ctypes.c_uint64(), ctypes.c_int()
+            h = rsa.rsa_exp_pair_trace(m.to_bytes(128, "big"), e.to_bytes(128, "big"), x.to_bytes(128, "big"), out,
+                                       ctypes.byref(ops), ctypes.byref(same))
+            assert same.value == 1
+            assert int.from_bytes(out.raw, "big") == pow(x, e, m), (nm, hex(x), hex(e))
+            traces.add((h, ops.value))
+    assert len(traces) == 1 and next(iter(traces))[1] == NOPS, traces
