@@ -17,110 +17,37 @@ namespace jfsx {
 
 // Slice-by-16 reads 20 random table dwords per 16 B; with one copy of each
 // table, 32 lanes of random bytes land on the 32 LDS banks with ~3.5-way
-// conflicts and the kernel is LDS-bound near 4.2 TB/s.  Here every byte lookup
-// is split into its two nibble lookups (the tables are linear: T[b] =
-// T[b & 15] ^ T[b & 240]) and each 16-entry nibble table is replicated 32x,
-// one replica per bank, so lane l always reads bank l mod 32: conflict-free at
-// twice the lookups.  A v_perm builds each address in one VALU op:
-//   perm(x & 0x0f0f0f0f, lb) = (lo nibble of byte k) << 8 | lb
-//   perm((x >> 4) & 0x0f0f0f0f, lb) = (hi nibble of byte k) << 8 | lb
-// with lb = 4 * (lane mod 32) | 0x10000 (byte 2 of lb is selected for the
-// tables above 64 KiB, past the ds_read offset field) and the table in the
-// ds_read immediate: table t (lo) / t + 0.5 (hi) at t * 4096 + hi * 128, nibble
-// stride 256 B -- 20 x 4 KiB = 80 KiB, two 16-wave workgroups per CU.
-// Tables t = 0..15 are U0..U15 (slice-by-16); t = 16..19 shift a lane CRC by
-// one 1 KiB row, so A' = S1024(A) ^ U(piece) and the 32 data lookups of a row
-// do not wait for A.  Each workgroup stages the tables once per task (0.5 to
-// 4 MiB) and every wave loops over segments.
-// JFSX_CRC_SPAN = 64 (default): in whole segments a lane owns 64 contiguous
-// bytes of every 4 KiB span (lane l: bytes 64l..64l+63), four 16-B pieces
-// chained through the slice-by-16 state (crc ^ first word, no lookups between
-// them), and the lane CRC moves from span to span by one 4096-B shift:
-// A' = S4096(A) ^ crc_raw(0, chunk) -- 34 nibble lookups per 16 B instead of
-// the 40 of the 16-B-per-lane rows (A' = S1024(A) ^ U(piece)).  Tables
-// t = 16..19 in LDS are then the 4096-B shift; the guarded path (ragged
-// segment ends) keeps 1 KiB rows and takes its 1024-B shift from global memory.
-// JFSX_CRC_BYTE = 1: slice-by-4 byte tables U12..U15 replicated once per bank
-// (table entry stride 256 B, two tables interleaved per 64 KiB: address =
-// byte << 8 | 4 * (lane mod 32) | region << 16, one v_perm each) -- 16
-// conflict-free lookups and about 28 VALU per 16 B instead of 34 and ~60,
-// at 144 KiB of LDS (one 16-wave workgroup per CU).  A lane's 64-B chunk is a
+// conflicts and the kernel is LDS-bound near 4.2 TB/s.  Here the tables are
+// the slice-by-4 byte tables U12..U15, each entry replicated 32x, one replica
+// per bank, so lane l always reads bank l mod 32: conflict-free.  A v_perm
+// builds each address in one VALU op (entry stride 256 B, two tables
+// interleaved per 64 KiB: address = byte << 8 | 4 * (lane mod 32) |
+// region << 16, with the region bytes carried in lb) -- 16 lookups and about
+// 28 VALU per 16 B at 144 KiB of LDS (one 16-wave workgroup per CU).
+// In whole segments a lane owns 64 contiguous bytes of every 4 KiB span, a
 // chain of 16 slice-by-4 steps; two spans' chains run interleaved, and the
-// 4096-B span shift keeps its nibble tables (region 2).
-// default since round 4: byte tables (JFSX_CRC_BYTE = 1) with quad-transposed
-// coalesced loads (JFSX_CRC_XPOSE = 1), 6.03-6.05 TB/s at 64 GiB against 5.33
-// for the nibble kernel on the same box (profiles/r4/ab_crc.txt)
-#ifndef JFSX_CRC_BYTE
-#define JFSX_CRC_BYTE 1
-#endif
-#ifndef JFSX_CRC_SPAN
-#define JFSX_CRC_SPAN 64
-#endif
+// lane CRC moves from span to span by one 4096-B shift, A' = S4096(A) ^
+// crc_raw(0, chunk), through nibble tables (the tables are linear: T[b] =
+// T[b & 15] ^ T[b & 240]) in region 2.  The guarded path (ragged segment
+// ends) keeps 1 KiB rows and takes its 1024-B shift from global memory.
+// Each workgroup stages the tables once per task (0.5 to 4 MiB) and every
+// wave loops over segments.  6.03-6.05 TB/s at 64 GiB against 5.33 for the
+// round-3 nibble-table kernel on the same box (profiles/r4/ab_crc.txt)
 constexpr uint32_t kCrcWaves = 16;
-#ifndef JFSX_CRC_PF
-#define JFSX_CRC_PF 4
-#endif
-constexpr int kCrcPf = JFSX_CRC_PF;  // rows of 16 B per lane in flight
-#if JFSX_CRC_BYTE
 constexpr uint32_t kCrcLds = 0x24000;  // 147456 B: byte tables 128 KiB + shift nibble tables 16 KiB
-#else
-constexpr uint32_t kCrcLds = 20 * 4096;  // 81920 B
-#endif
 
-#define NIB(t, h, xm, k)                                                                                          \
-    lds_u32(lds, __builtin_amdgcn_perm((xm), lb, ((t) >= 16 ? 0x0c020000u : 0x0c0c0000u) | ((4u + (k)) << 8)) + \
-                     (((t)&15) * 4096u + (h)*128u))
-#define X3(a, b, c) __builtin_amdgcn_bitop3_b32((a), (b), (c), 0x96)
-
-// the 8 nibble lookups of word x through tables t..t+3
-__device__ __forceinline__ uint32_t crc_word_nib(const char *lds, uint32_t lb, uint32_t t, uint32_t x) {
-    const uint32_t xl = x & 0x0f0f0f0fu, xh = (x >> 4) & 0x0f0f0f0fu;
-    return X3(X3(NIB(t, 0, xl, 0), NIB(t, 1, xh, 0), NIB(t + 1, 0, xl, 1)),
-              X3(NIB(t + 1, 1, xh, 1), NIB(t + 2, 0, xl, 2), NIB(t + 2, 1, xh, 2)),
-              NIB(t + 3, 0, xl, 3) ^ NIB(t + 3, 1, xh, 3));
-}
-
-// A advanced over one 1 KiB row whose lane piece is p:
-// crc_raw(shift(A, 1008 B), p) = shift(A, 1024 B) ^ crc_raw(0, p)
-__device__ __forceinline__ uint32_t crc_row_nib(const char *lds, uint32_t lb, uint32_t A, uint4 p) {
-    const uint32_t d = X3(crc_word_nib(lds, lb, 0, p.x), crc_word_nib(lds, lb, 4, p.y), crc_word_nib(lds, lb, 8, p.z)) ^
-                       crc_word_nib(lds, lb, 12, p.w);
-    return crc_word_nib(lds, lb, 16, A) ^ d;
-}
-#undef X3
-
-// crc_raw(0, 16-byte piece p) through the LDS nibble tables U0..U15
-__device__ __forceinline__ uint32_t crc_u16_nib(const char *lds, uint32_t lb, uint32_t x, uint32_t y, uint32_t z,
-                                                uint32_t w) {
-#define X3(a, b, c) __builtin_amdgcn_bitop3_b32((a), (b), (c), 0x96)
-    return X3(crc_word_nib(lds, lb, 0, x), crc_word_nib(lds, lb, 4, y), crc_word_nib(lds, lb, 8, z)) ^
-           crc_word_nib(lds, lb, 12, w);
-#undef X3
-}
-
-#ifndef JFSX_CRC_CHAINS
-#define JFSX_CRC_CHAINS 2
-#endif
-#ifndef JFSX_CRC_XPOSE
-#define JFSX_CRC_XPOSE 1
-#endif
-// the lane's 64-byte chunk of span r of a segment: piece j.  XPOSE = 0: lane l
-// owns bytes 64l..64l+63 (each load instruction touches 32 cache lines, 32 B
-// of each).  XPOSE = 1: instruction j loads the span's bytes 1024j + 16l
-// (one fully coalesced 1 KiB row, 8 whole lines); after quad_xpose lane
-// l = 4m + t holds the chunk at 64 (16t + m) of the span.
-// JFSX_CRC_NT = 1: the loads carry the non-temporal hint (the data is read
-// once; A/B in profiles/r4/ab_crc.txt)
-#ifndef JFSX_CRC_NT
-#define JFSX_CRC_NT 1
-#endif
-__device__ __forceinline__ uint4 crc_ld16(const uint8_t *p) { return JFSX_CRC_NT ? gld16_nt(p) : gld16(p); }
+// the lane's 64-byte chunk of span r of a segment: piece j.  Instruction j
+// loads the span's bytes 1024j + 16l (one fully coalesced 1 KiB row, 8 whole
+// lines; with 64l + 16j each load would touch 32 cache lines, 32 B of each);
+// after quad_xpose lane l = 4m + t holds the chunk at 64 (16t + m) of the
+// span.  The loads carry the non-temporal hint (the data is read once; A/B
+// in profiles/r4/ab_crc.txt)
 __device__ __forceinline__ uint4 crc_chunk_ld(const uint8_t *seg, uint32_t lane, int r, int j) {
-    return JFSX_CRC_XPOSE ? crc_ld16(seg + 4096 * r + 1024 * j + 16 * lane) : crc_ld16(seg + 4096 * r + 64 * lane + 16 * j);
+    return gld16_nt(seg + 4096 * r + 1024 * j + 16 * lane);
 }
 // lane chunk index within a span (the final shift to the segment end)
 __device__ __forceinline__ uint32_t crc_chunk_idx(uint32_t lane) {
-    return JFSX_CRC_XPOSE ? 16u * (lane & 3u) + (lane >> 2) : lane;
+    return 16u * (lane & 3u) + (lane >> 2);
 }
 // 4 x 4 transpose of 16-byte pieces across the 4 lanes of a quad: afterwards
 // v[i] of lane t is what v[t] of lane i held.  Two butterfly stages (lane bit
@@ -144,7 +71,6 @@ __device__ __forceinline__ void quad_xpose(uint4 (&v)[4], uint32_t lane) {
     XS(x) XS(y) XS(z) XS(w)
 #undef XS
 }
-#if JFSX_CRC_BYTE
 // byte k of x through U(12 + k): region k >> 1 (lb byte 2 = 1), half k & 1
 #define BYT(x, k)                                                                                              \
     lds_u32(lds, __builtin_amdgcn_perm((x), lb, 0x0c000000u | ((k) >= 2 ? 0x00020000u : 0x000c0000u) |        \
@@ -173,18 +99,13 @@ __device__ __forceinline__ uint32_t crc_u16_byte(const char *lds, uint32_t lb, u
     c = crc_step4(lds, lb, c ^ p.z);
     return crc_step4(lds, lb, c ^ p.w);
 }
-#endif
 
 // the guarded path's row step with the 1024-B shift from global byte tables
 __device__ __forceinline__ uint32_t crc_row_g(const char *lds, const uint32_t *__restrict__ T, uint32_t lb, uint32_t A,
                                               uint4 p) {
     const uint32_t s = T[24 * 256 + (A & 0xffu)] ^ T[25 * 256 + ((A >> 8) & 0xffu)] ^
                        T[26 * 256 + ((A >> 16) & 0xffu)] ^ T[27 * 256 + (A >> 24)];
-#if JFSX_CRC_BYTE
     return crc_u16_byte(lds, lb, p) ^ s;
-#else
-    return crc_u16_nib(lds, lb, p.x, p.y, p.z, p.w) ^ s;
-#endif
 }
 
 // ragged tails (segment length not a multiple of 16 B: the last segment of an
@@ -200,16 +121,14 @@ __device__ __noinline__ uint32_t crc_partial_g(const uint32_t *__restrict__ T, u
     return c;
 }
 
-#ifndef JFSX_CRC_WPE
-#define JFSX_CRC_WPE (JFSX_CRC_BYTE ? 4 : 8)
-#endif
-__global__ __launch_bounds__(kCrcWaves * 64) __attribute__((amdgpu_waves_per_eu(JFSX_CRC_WPE))) void crc_segments_k(const Task *__restrict__ tasks,
+constexpr int kCrcWpe = 4;     // waves per SIMD the compiler plans for (one 16-wave workgroup per CU)
+constexpr int kCrcChains = 2;  // spans whose slice-by-4 chains run interleaved
+__global__ __launch_bounds__(kCrcWaves * 64) __attribute__((amdgpu_waves_per_eu(kCrcWpe))) void crc_segments_k(const Task *__restrict__ tasks,
                                                                 const BlkDev *__restrict__ blks, DevTables tab) {
     __shared__ __attribute__((aligned(16))) char lds[kCrcLds];
     const Task task = tasks[blockIdx.x];
     const BlkDev blk = blks[task.blk];
     const uint32_t tid = threadIdx.x;
-#if JFSX_CRC_BYTE
     // stage: byte tables U12..U15, i = (table t, entry e, replica quad rq)
     for (uint32_t i = tid; i < 4 * 256 * 8; i += kCrcWaves * 64) {
         const uint32_t rq = i & 7, e = (i >> 3) & 255, t = i >> 11;
@@ -227,28 +146,16 @@ __global__ __launch_bounds__(kCrcWaves * 64) __attribute__((amdgpu_waves_per_eu(
     __syncthreads();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const uint32_t lb = ((lane & 31) << 2) | 0x10000u | 0x2000000u;
-#else
-    // stage: i = (table t, hi, nibble, replica quad rq)
-    for (uint32_t i = tid; i < 640 * 8; i += kCrcWaves * 64) {
-        const uint32_t rq = i & 7, nib = (i >> 3) & 15, hi = (i >> 7) & 1, t = i >> 8;
-        const uint32_t v = tab.crc[(t < 16 ? t : t + (JFSX_CRC_SPAN >= 64 ? 12 : 8)) * 256 + (hi ? nib << 4 : nib)];
-        *reinterpret_cast<uint4 *>(lds + t * 4096 + nib * 256 + hi * 128 + 16 * rq) = make_uint4(v, v, v, v);
-    }
-    __syncthreads();
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const uint32_t lb = ((lane & 31) << 2) | 0x10000u;
-#endif
     const uint8_t *src = blk.src;
     for (uint64_t seg0 = task.c0 + (uint64_t)wave * kSeg; seg0 < task.c1; seg0 += (uint64_t)kCrcWaves * kSeg) {
         const uint64_t seg1 = seg0 + kSeg < task.c1 ? seg0 + kSeg : task.c1;
         uint32_t A = 0, lend = 0;
         const uint64_t nrows = (seg1 - seg0 + 1023) / 1024;
-        if (JFSX_CRC_BYTE && seg1 - seg0 == (uint64_t)kSeg) {
-#if JFSX_CRC_BYTE
+        if (seg1 - seg0 == (uint64_t)kSeg) {
             // full segment, 64-B lane chunks of the 8 spans of 4 KiB; CH spans
             // are CH independent slice-by-4 chains, and each piece's load for
             // the span CH further on is issued as soon as the piece is consumed
-            constexpr int CH = JFSX_CRC_CHAINS;
+            constexpr int CH = kCrcChains;
             uint4 buf[CH][4];
 #pragma unroll
             for (int k = 0; k < CH; k++)
@@ -256,10 +163,8 @@ __global__ __launch_bounds__(kCrcWaves * 64) __attribute__((amdgpu_waves_per_eu(
                 for (int j = 0; j < 4; j++) buf[k][j] = crc_chunk_ld(src + seg0, lane, k, j);
 #pragma unroll
             for (int r = 0; r < 8; r += CH) {
-                if (JFSX_CRC_XPOSE) {
 #pragma unroll
-                    for (int k = 0; k < CH; k++) quad_xpose(buf[k], lane);
-                }
+                for (int k = 0; k < CH; k++) quad_xpose(buf[k], lane);
                 // x = state ^ next word; each step folds the next word into
                 // its 4-way XOR (two v_bitop3)
                 uint32_t x[CH];
@@ -294,54 +199,12 @@ __global__ __launch_bounds__(kCrcWaves * 64) __attribute__((amdgpu_waves_per_eu(
                 for (int k = 0; k < CH; k++) A = crc_step4x(lds, lb, x[k], crc_shift4096(lds, lb, A));
             }
             lend = kSeg;
-#endif
-        } else if (!JFSX_CRC_BYTE && JFSX_CRC_SPAN >= 64 && seg1 - seg0 == (uint64_t)kSeg) {
-            // full segment: spans of 64 x SPAN bytes, lane chunk SPAN bytes
-            // (P pieces); each piece's load for the next span is issued as
-            // soon as the piece is consumed
-            constexpr int P = JFSX_CRC_SPAN / 16, NSP = 32768 / (64 * JFSX_CRC_SPAN);
-            const uint8_t *q = src + seg0 + JFSX_CRC_SPAN * lane;
-            static_assert(!JFSX_CRC_XPOSE || JFSX_CRC_SPAN == 64, "quad transpose needs 64-B lane chunks");
-            uint4 buf[P];
-#pragma unroll
-            for (int j = 0; j < P; j++) buf[j] = JFSX_CRC_XPOSE ? crc_chunk_ld(src + seg0, lane, 0, j) : gld16(q + 16 * j);
-#pragma unroll
-            for (int r = 0; r < NSP; r++) {
-                uint32_t c = 0;
-#if JFSX_CRC_XPOSE
-                quad_xpose(buf, lane);
-#endif
-#pragma unroll
-                for (int j = 0; j < P; j++) {
-                    const uint4 p = buf[j];
-                    if (r + 1 < NSP)
-                        buf[j] = JFSX_CRC_XPOSE ? crc_chunk_ld(src + seg0, lane, r + 1, j)
-                                                : gld16(q + 64 * JFSX_CRC_SPAN * (r + 1) + 16 * j);
-                    c = crc_u16_nib(lds, lb, p.x ^ c, p.y, p.z, p.w);
-                }
-                A = crc_word_nib(lds, lb, 16, A) ^ c;
-            }
-            lend = kSeg;  // marker: lane chunk ends at 32768 - SPAN * (63 - lane)
-        } else if (JFSX_CRC_SPAN < 64 && seg1 - seg0 == (uint64_t)kSeg) {
-            // full segment: 32 rows, kCrcPf loads in flight per wave (HBM
-            // latency x 8 TB/s needs ~64 KiB in flight per CU)
-            const uint8_t *q = src + seg0 + 16 * lane;
-            uint4 buf[kCrcPf];
-#pragma unroll
-            for (int r = 0; r < kCrcPf; r++) buf[r] = gld16(q + 1024 * r);
-#pragma unroll
-            for (int r = 0; r < 32; r++) {
-                const uint4 p = buf[r % kCrcPf];
-                if (r + kCrcPf < 32) buf[r % kCrcPf] = gld16(q + 1024 * (r + kCrcPf));
-                A = crc_row_nib(lds, lb, A, p);
-            }
-            lend = kSeg - 1024 + 16 * lane + 16;
         } else {
             for (uint64_t r = 0; r < nrows; r++) {
                 const uint64_t o = seg0 + 1024 * r + 16 * lane;
                 const uint4 p = load_piece(src, o, seg1);
                 if (o + 16 <= seg1) {
-                    A = JFSX_CRC_SPAN >= 64 ? crc_row_g(lds, tab.crc, lb, A, p) : crc_row_nib(lds, lb, A, p);
+                    A = crc_row_g(lds, tab.crc, lb, A, p);
                     lend = (uint32_t)(o + 16 - seg0);
                 } else if (o < seg1) {
                     const uint32_t pw[4] = {p.x, p.y, p.z, p.w};
@@ -353,15 +216,8 @@ __global__ __launch_bounds__(kCrcWaves * 64) __attribute__((amdgpu_waves_per_eu(
         const uint32_t Lseg = (uint32_t)(seg1 - seg0);
         uint32_t v, K;
         if (Lseg == (uint32_t)kSeg) {
-            if (JFSX_CRC_SPAN >= 64) {
-                // lane chunk end to segment end: SPAN * (63 - lane) bytes =
-                // crcx[128 + lane] (64 * (63 - lane) bytes) squared SPAN / 64 - 1 times
-                uint32_t x = tab.crcx[128 + crc_chunk_idx(lane)];
-                for (int k = 64; k < JFSX_CRC_SPAN; k <<= 1) x = crc_mulmod(x, x);
-                v = crc_mulmod(x, A);
-            } else {
-                v = crc_mulmod(tab.crcx[lane], A);
-            }
+            // lane chunk end to segment end: 64 * (63 - chunk index) bytes
+            v = crc_mulmod(tab.crcx[128 + crc_chunk_idx(lane)], A);
             K = tab.crcx[96];
         } else {
             v = crc_mulmod(crc_xpow8(Lseg - lend, tab.crcx + 64), A);
@@ -398,8 +254,8 @@ __global__ __launch_bounds__(kCrcWaves * 64) __attribute__((amdgpu_waves_per_eu(
 // (crc_chunk_mul, 1024 words built by the host).  That is 8 conflict-free
 // lookups per span, what the span shift costs crc_segments_k, against about
 // 190 VALU operations for a crc_mulmod -- more than the 16 table steps of the
-// span itself.  The 8 lanes of a chunk are then XORed together: with
-// JFSX_CRC_XPOSE they are the lanes 4 apart inside a 32-lane half (lane bits
+// span itself.  The 8 lanes of a chunk are then XORed together: after the
+// quad transpose they are the lanes 4 apart inside a 32-lane half (lane bits
 // 2..4), reduced by two DPP row rotates (row_ror:4, row_ror:8: all lanes of a
 // 16-lane row with the same lane & 3) and one ds_swizzle (xor 16); no LDS
 // memory and no barrier.  K512 = x^(8 * 512) * 0xffffffff, the init/xorout
@@ -409,19 +265,12 @@ __global__ __launch_bounds__(kCrcWaves * 64) __attribute__((amdgpu_waves_per_eu(
 // file through the global byte table, and for the file's short last chunk a
 // crc_mulmod by the distance to its end.
 __device__ __forceinline__ uint32_t chunk_xor8(uint32_t v) {
-#if JFSX_CRC_XPOSE
     v ^= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x124, 0xF, 0xF, true);  // row_ror:4
     v ^= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x128, 0xF, 0xF, true);  // row_ror:8
     v ^= (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401F);              // lane ^ 16
-#else
-    v ^= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);  // lane ^ 1
-    v ^= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true);  // lane ^ 2
-    v ^= (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x101F);             // lane ^ 4
-#endif
     return v;
 }
 
-#if JFSX_CRC_BYTE
 // one span [s0, min(s0 + 4096, end)) of a file, every load guarded
 __device__ __noinline__ void crc_chunks_span_g(const char *lds, uint32_t lb, const uint32_t *__restrict__ T,
                                                const uint32_t *__restrict__ crcx, const uint8_t *src, uint64_t s0,
@@ -460,7 +309,7 @@ __device__ __noinline__ void crc_chunks_span_g(const char *lds, uint32_t lb, con
     if ((ci & 7u) == 0 && cs < end) out[cs >> 9] = __builtin_bswap32(~(K ^ raw));
 }
 
-__global__ __launch_bounds__(kCrcWaves * 64) __attribute__((amdgpu_waves_per_eu(JFSX_CRC_WPE))) void crc_chunks_k(
+__global__ __launch_bounds__(kCrcWaves * 64) __attribute__((amdgpu_waves_per_eu(kCrcWpe))) void crc_chunks_k(
     const Task *__restrict__ tasks, const BlkDev *__restrict__ blks, DevTables tab,
     const uint32_t *__restrict__ crc_chunk_mul, uint32_t K512) {
     __shared__ __attribute__((aligned(16))) char lds[kCrcLds];
@@ -496,7 +345,7 @@ __global__ __launch_bounds__(kCrcWaves * 64) __attribute__((amdgpu_waves_per_eu(
         }
         // a whole 32 KiB run: the loop of crc_segments_k's default path, with
         // the span shift replaced by the chunk combine
-        constexpr int CH = JFSX_CRC_CHAINS;
+        constexpr int CH = kCrcChains;
         uint4 buf[CH][4];
 #pragma unroll
         for (int k = 0; k < CH; k++)
@@ -504,10 +353,8 @@ __global__ __launch_bounds__(kCrcWaves * 64) __attribute__((amdgpu_waves_per_eu(
             for (int j = 0; j < 4; j++) buf[k][j] = crc_chunk_ld(src + seg0, lane, k, j);
 #pragma unroll
         for (int r = 0; r < 8; r += CH) {
-            if (JFSX_CRC_XPOSE) {
 #pragma unroll
-                for (int k = 0; k < CH; k++) quad_xpose(buf[k], lane);
-            }
+            for (int k = 0; k < CH; k++) quad_xpose(buf[k], lane);
             uint32_t x[CH];
 #pragma unroll
             for (int k = 0; k < CH; k++) x[k] = buf[k][0].x;
@@ -545,7 +392,6 @@ __global__ __launch_bounds__(kCrcWaves * 64) __attribute__((amdgpu_waves_per_eu(
         }
     }
 }
-#endif
 
 // Hadoop file checksum, block phase: lane b hashes the nw[b] chunk-CRC words
 // of DFS block b (4 * min(crcPerBlock, chunks left) bytes at words + w0[b];

@@ -14,7 +14,6 @@ __device__ __forceinline__ uint4 lds_u4(const char *lds, uint32_t byteaddr) {
 // 4 * byte k of x in one VALU op: v_lshlrev_b32 with an SDWA byte select on the
 // shifted operand.  With the table base below 64 KiB the base folds into the
 // ds_read offset, so a table lookup costs one VALU op instead of two or three.
-#if JFSX_CRCSDWA
 template <int K>
 __device__ __forceinline__ uint32_t byte_x4(uint32_t x) {
     uint32_t r;
@@ -28,21 +27,7 @@ __device__ __forceinline__ uint32_t byte_x4(uint32_t x) {
         asm("v_lshlrev_b32_sdwa %0, 2, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(r) : "v"(x));
     return r;
 }
-#ifdef JFSX_ABLATE_CRCBANK
-// timing experiment only (wrong CRCs): every lookup keeps its SDWA address op
-// plus one v_and_or_b32, but lands in the lane's own bank (conflict-free)
-__device__ __forceinline__ uint32_t abl_bank(uint32_t a) {
-    uint32_t r;
-    asm volatile("v_and_or_b32 %0, %1, 0, %2" : "=v"(r) : "v"(a), "v"((threadIdx.x & 31u) << 2));
-    return r;
-}
-#define CRC_T(t, x, k) lds_u32(lds, abl_bank(byte_x4<(k)>(x)) + CB + 1024u * (t))
-#else
 #define CRC_T(t, x, k) lds_u32(lds, byte_x4<(k)>(x) + CB + 1024u * (t))
-#endif
-#else
-#define CRC_T(t, x, k) lds_u32(lds, ((((x) >> (8 * (k))) & 0xffu) << 2) + CB + 1024u * (t))
-#endif
 
 // crc_raw(A, 16-byte piece) = crc_raw(0, piece ^ shift(A, 1008 B) in the first word)
 // S = 16: shift by 1008 B first; S = 20: shift by 4032 B; S < 0: no shift
@@ -85,11 +70,7 @@ __device__ __forceinline__ CrcL1Base crc_l1_base(const uint32_t *gcrc) {
 template <int I>
 __device__ __forceinline__ uint32_t crc_l1_term(const CrcL1Base &g, uint4 p) {
     const uint32_t w = I < 4 ? p.y : (I < 8 ? p.z : p.w);
-#if JFSX_CRCSDWA
     const uint32_t o = byte_x4<(I & 3)>(w);
-#else
-    const uint32_t o = ((w >> (8 * (I & 3))) & 0xffu) << 2;
-#endif
     const __attribute__((address_space(1))) char *t = (const __attribute__((address_space(1))) char *)(I < 8 ? g.a : g.b);
     return *(gcu32 *)(t + o + (1024 * (4 + I) - (I < 8 ? 8192 : 12288)));
 }
@@ -160,14 +141,14 @@ __device__ __forceinline__ void gst16_nt(uint8_t *p, uint4 v) {
     v4u w = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(w, (gv4u *)(p));
 }
-// the AEAD kernels' block streams (plaintext in, ciphertext out): JFSX_AEAD_NT
-// bit 1 gives the loads, bit 2 the stores the non-temporal hint (A/B)
-#ifndef JFSX_AEAD_NT
-#define JFSX_AEAD_NT 0
-#endif
-__device__ __forceinline__ uint4 ald16(const uint8_t *p) { return (JFSX_AEAD_NT & 1) ? gld16_nt(p) : gld16(p); }
+// the AEAD kernels' block streams (plaintext in, ciphertext out): bit 1 of NT
+// gives the loads, bit 2 the stores the non-temporal hint (each kernel file
+// fixes its own kAeadNt)
+template <int NT>
+__device__ __forceinline__ uint4 ald16(const uint8_t *p) { return (NT & 1) ? gld16_nt(p) : gld16(p); }
+template <int NT>
 __device__ __forceinline__ void ast16(uint8_t *p, uint4 v) {
-    if (JFSX_AEAD_NT & 2)
+    if (NT & 2)
         gst16_nt(p, v);
     else
         gst16(p, v);

@@ -22,15 +22,7 @@
 //   * gcm_finalize: one wave per block.  Lifts each wave partial by
 //     H^(blocks after that wave), XORs, adds E_K(J0)^len-block -> tag; in Open
 //     compares the tag; in VERIFY compares CRCs (first failing segment).
-#include <cstdio>
-#include <cstdlib>
 
-// plaintext in and ciphertext out as non-temporal block streams (coalesced
-// 1 KiB rows, read or written once): +0.7 % same box (profiles/r4/ab_gcm_rows.txt;
-// the ChaCha kernel's 64-byte lane runs lose 33 % with the hint and keep 0)
-#ifndef JFSX_AEAD_NT
-#define JFSX_AEAD_NT 3
-#endif
 #include "jfsx_dev.h"
 
 #define JFSX_HD __device__ __forceinline__
@@ -52,12 +44,9 @@ namespace jfsx {
 // directly, the AES base as 0x10000 (bit 16 of the lane's v_perm operand loff)
 // plus the offset 20K.  So no lookup spends a VALU op on its base.
 // ---------------------------------------------------------------------------
-// JFSX_GF_CT_LIFT (default 1): the main kernel's per-lane GHASH lifts by
-// g_mul_ct instead of the bit-serial g_mul (A/B builds)
-#ifndef JFSX_GF_CT_LIFT
-#define JFSX_GF_CT_LIFT 1
-#endif
-
+// plaintext in and ciphertext out as non-temporal block streams (coalesced
+// 1 KiB rows, read or written once): +0.7 % same box (profiles/r4/ab_gcm_rows.txt)
+constexpr int kAeadNt = 3;
 constexpr uint32_t kLdsCrc = 0;
 constexpr uint32_t kLdsGh = 20480;              // GHASH T[b][j]: kLdsGh + (b << 8) | (j << 4)
 constexpr uint32_t kLdsAesOff = 20480;          // ds_read offset of the AES table
@@ -76,7 +65,7 @@ __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
 // round key i as the T-table rounds consume it (pre-rotated for rounds 2..13, see AES_COL)
 __device__ __forceinline__ uint32_t rk_load(const uint32_t *rk, int i) {
     uint32_t k = rk[i];
-    if (JFSX_RKR && i >= 8 && i < 56) {
+    if (i >= 8 && i < 56) {
         k = (k >> 8) | (k << 24);
         OPAQUE(k);  // keep it in an SGPR (a VALU rotate would cost 48 VGPRs)
     }
@@ -91,18 +80,12 @@ __device__ __forceinline__ uint32_t rk_load(const uint32_t *rk, int i) {
 #define TB(w, k) lds_u32(lds, __builtin_amdgcn_perm((w), loff, AES_SEL(k)) + (kLdsAesOff + 128u))
 
 // One full AES round on LE column words.  T1 = rotl8 T0 and T3 = rotl8 T2, and
-// rotl8(a) ^ rotl8(b) = rotl8(a ^ b), so a column costs 4 v_perm (addresses),
-// 4 ds_read_b32, one xor, one alignbit and one 3-input xor (v_bitop3 0x96).
-#if JFSX_RKR
-// rounds 2..13 hold their round keys pre-rotated (rk_load: rotr8), so the key
-// joins the rotated pair's 3-input XOR and a column is 4 v_perm, 4 ds_read_b32,
-// two v_bitop3 and one alignbit
+// rotl8(a) ^ rotl8(b) = rotl8(a ^ b); rounds 2..13 hold their round keys
+// pre-rotated (rk_load: rotr8), so the key joins the rotated pair's 3-input
+// XOR and a column is 4 v_perm (addresses), 4 ds_read_b32, two v_bitop3 (0x96)
+// and one alignbit
 #define AES_COL(o, i0, i1, i2, i3, rkv) \
     o = xor3(TA(i0, 0), TB(i2, 2), rotl8(xor3(TA(i1, 1), TB(i3, 3), (rkv))));
-#else
-#define AES_COL(o, i0, i1, i2, i3, rkv) \
-    o = xor3(TA(i0, 0), TB(i2, 2), rotl8(TA(i1, 1) ^ TB(i3, 3))) ^ (rkv);
-#endif
 #define AES_ROUND(o0, o1, o2, o3, i0, i1, i2, i3, r) \
     AES_COL(o0, i0, i1, i2, i3, rk[4 * (r) + 0])     \
     AES_COL(o1, i1, i2, i3, i0, rk[4 * (r) + 1])     \
@@ -160,20 +143,14 @@ __device__ __forceinline__ void aes_r2_uniform(const char *lds, uint32_t loff, c
     const uint32_t a1 = k1[1] ^ TB(x3, 2);
     const uint32_t a2 = k1[2] ^ rotl8(TA(x3, 1));
     const uint32_t a3 = k1[3] ^ TA(x3, 0);
-#if JFSX_RKR
     u[0] = xor3(TB(a2, 2), rotl8(xor3(TA(a1, 1), TB(a3, 3), rk[8])), 0u);
     u[1] = xor3(TA(a1, 0), TB(a3, 2), rotl8(TA(a2, 1) ^ rk[9]));
     u[2] = xor3(TA(a2, 0), rotl8(xor3(TA(a3, 1), TB(a1, 3), rk[10])), 0u);
     u[3] = xor3(TA(a3, 0), TB(a1, 2), rotl8(TB(a2, 3) ^ rk[11]));
-#else
-    u[0] = xor3(TB(a2, 2), rotl8(TA(a1, 1) ^ TB(a3, 3)), rk[8]);
-    u[1] = xor3(TA(a1, 0), TB(a3, 2), rotl8(TA(a2, 1))) ^ rk[9];
-    u[2] = xor3(TA(a2, 0), rotl8(TA(a3, 1) ^ TB(a1, 3)), rk[10]);
-    u[3] = xor3(TA(a3, 0), TB(a1, 2), rotl8(TB(a2, 3))) ^ rk[11];
-#endif
 }
 
-// aes_ctr_blocks with rounds 1-2 taken from the lane's counter-uniform terms u;
+// Keystream blocks of NS rows (the chains interleave for ILP) with rounds 1-2
+// taken from the lane's counter-uniform terms u;
 // ks comes out without the last round key (rk[56..59]).
 // side(AesStep<i>) runs after the i-th of the 12 round groups (rounds 1-2, then
 // 3 .. 13): the caller's place for work that fills the rounds' latency (the
@@ -274,9 +251,9 @@ __device__ __forceinline__ void gh_rho(const uint32_t a[4], const GhLane &g, uin
     uint32_t u[4];
 #pragma unroll
     // v_perm with a per-lane whole-dword selector: no VCC to rebuild per select
-    for (int i = 0; i < 4; i++) u[i] = JFSX_GHPERM ? PERM(a[(i + 2) & 3], a[i], g.p2) : (g.r2 ? a[(i + 2) & 3] : a[i]);
+    for (int i = 0; i < 4; i++) u[i] = PERM(a[(i + 2) & 3], a[i], g.p2);
 #pragma unroll
-    for (int i = 0; i < 4; i++) R[i] = JFSX_GHPERM ? PERM(u[(i + 1) & 3], u[i], g.p1) : (g.r1 ? u[(i + 1) & 3] : u[i]);
+    for (int i = 0; i < 4; i++) R[i] = PERM(u[(i + 1) & 3], u[i], g.p1);
 }
 // a = rho^-1(R): a[i] = R[(i - k) & 3]
 __device__ __forceinline__ void gh_rho_inv(const uint32_t R[4], const GhLane &g, uint32_t a[4]) {
@@ -465,25 +442,15 @@ __device__ __noinline__ Stream row_generic(char *lds, uint32_t loff, const GhLan
     return st;
 }
 
-// gcm_main: one workgroup per task; each wave runs NS streams in lock-step.
-// BS = 0: T-table AES in LDS, 16 waves (4/SIMD, <= 128 VGPRs).
-// BS = 1: whole 32 KiB segments use the bitsliced AES on the VALU
-//         (jfsx_aes_bs.h; 128 VGPRs of state), 8 waves (2/SIMD, <= 256 VGPRs).
-// BS = 2: hybrid, 8 waves of the BS = 1 shape: the last nbs waves run the
-//         bitsliced AES on whole segments at the front of the task, the other
-//         8 - nbs waves split the rest by rows with the T-table AES at a
-//         raised priority, so the LDS pipe the T-table waves feed and the VALU
-//         the bitsliced waves fill run at once (hyb below).
-template <int BS>
+// gcm_main: one workgroup per task, one stream (a contiguous byte range) per wave.
+// BS = false: T-table AES in LDS, 16 waves (4/SIMD, <= 128 VGPRs).
+// BS = true:  whole 32 KiB segments use the bitsliced AES on the VALU
+//             (jfsx_aes_bs.h; 128 VGPRs of state), 8 waves (2/SIMD, <= 256 VGPRs).
+template <bool BS>
 struct GcmShape {
     static constexpr uint32_t waves = BS ? 8u : (uint32_t)kWaves;
     static constexpr uint32_t threads = waves * 64u;
 };
-// hybrid split (BS = 2), a kernel argument: bits 0..3 nbs (bitsliced waves),
-// bits 8..15 rho = 16 x (bitsliced wave rate / T-table wave rate), bits 16..17
-// the T-table waves' s_setprio level
-__device__ __forceinline__ uint32_t hyb_nbs(uint32_t h) { return h & 15u; }
-__device__ __forceinline__ uint32_t hyb_rho(uint32_t h) { return (h >> 8) & 255u; }
 
 // JFSX_KS_PHASES probe build: the workgroup running block 0's first task
 // stamps the 100 MHz clock at the main kernel's phase boundaries (g_main_ts:
@@ -513,12 +480,11 @@ __device__ uint64_t g_wgtrace[4 * 65536];
 // from the vector L1 instead of the LDS (crc_piece_l1; 0: all from the LDS).
 // Only where the CRC covers the loaded side, so the gathers can be issued
 // inside the AES rounds, long before the step that needs them.
-template <bool OPEN, int CRCMODE, int NS, int BS, int KL1>
+template <bool OPEN, int CRCMODE, bool BS, int KL1>
 __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDev *__restrict__ blks,
                                          const GcmSched *__restrict__ sched, uint32_t *__restrict__ partial,
                                          uint32_t *__restrict__ pexp, const DevTables &tab, uint32_t tid,
-                                         uint32_t wave, uint32_t lane, uint32_t loff, const GhLane &gl, uint32_t xl,
-                                         uint32_t hyb) {
+                                         uint32_t wave, uint32_t lane, uint32_t loff, const GhLane &gl, uint32_t xl) {
 #ifdef JFSX_ABLATE_TRACE
     const uint64_t trace_t0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -561,78 +527,42 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
     MAIN_STAMP(first_task, 2);
     const uint64_t c0 = task.c0, c1 = task.c1;
     const uint32_t nseg = (uint32_t)((c1 - c0 + kSeg - 1) / kSeg);
-    constexpr uint32_t V = GcmShape<BS>::waves * NS;  // virtual waves (streams) per task
+    constexpr uint32_t V = GcmShape<BS>::waves;  // waves (streams) per task
 
-    // Row split (T-table kernel, one stream per wave): the task's rows are cut
-    // into 16 contiguous runs of equal length, so a task of any size keeps
-    // every wave busy (a 64 KiB block has 2 segments: with whole segments per
-    // wave 14 of 16 waves would idle).  A segment shared by two waves gets its
-    // CRC from both waves' raw shares (crc_segment_end, task end below).  The
+    // Row split (T-table kernel): the task's rows are cut into 16 contiguous
+    // runs of equal length, so a task of any size keeps every wave busy (a
+    // 64 KiB block has 2 segments: with whole segments per wave 14 of 16
+    // waves would idle).  A segment shared by two waves gets its CRC from
+    // both waves' raw shares (crc_segment_end, task end below).  The
     // bitsliced kernel keys whole 32 KiB segments and keeps the segment split.
-    constexpr bool kRowSplit = !BS && NS == 1;
-    // segments shared by two waves' row ranges (their CRC from raw shares)
-    constexpr bool kShares = kRowSplit || (BS == 2 && NS == 1);
-    // hybrid: waves [nt, 8) are bitsliced and take q whole segments each from
-    // the front of the task; waves [0, nt) row-split the rest
-    const uint32_t nbs = BS == 2 ? hyb_nbs(hyb) : 0u, nt = GcmShape<BS>::waves - nbs;
-    const bool isbs = BS == 1 || (BS == 2 && wave >= nt);
-    uint32_t q = 0;
-    if (BS == 2 && nbs) {
-        const uint32_t rho = hyb_rho(hyb), whole = (uint32_t)((c1 - c0) / kSeg);
-        q = nseg * rho / (nbs * rho + nt * 16u);
-        if (nbs * q > whole) q = whole / nbs;
+    constexpr bool kRowSplit = !BS;
+    Stream st;
+    if (kRowSplit) {
+        // in pairs of rows: every stream starts on an even row, as the two-row
+        // loop's segment-end test assumes (only its second row can end a segment)
+        const uint32_t npairs = (uint32_t)((c1 - c0 + 2047) / 2048);
+        const uint32_t ra = 2 * (wave * npairs / V), rb = 2 * ((wave + 1) * npairs / V);
+        st.sub0 = c0 + (uint64_t)ra * 1024;
+        st.sub1 = rb > ra ? (c0 + (uint64_t)rb * 1024 < c1 ? c0 + (uint64_t)rb * 1024 : c1) : st.sub0;
+    } else {
+        const uint32_t sa = wave * nseg / V, sb = (wave + 1) * nseg / V;
+        st.sub0 = c0 + (uint64_t)sa * kSeg;
+        st.sub1 = sb > sa ? (c0 + (uint64_t)sb * kSeg < c1 ? c0 + (uint64_t)sb * kSeg : c1) : st.sub0;
     }
-    const uint64_t tt0 = c0 + (uint64_t)nbs * q * kSeg;  // the T-table waves' region [tt0, c1)
-    // in pairs of rows: every stream starts on an even row, as the two-row
-    // loop's segment-end test assumes (only its second row can end a segment)
-    const uint32_t npairs = (uint32_t)((c1 - c0 + 2047) / 2048);
-    Stream st[NS];
-#pragma unroll
-    for (int s = 0; s < NS; s++) {
-        const uint32_t v = wave * NS + s;
-        if (BS == 2 && isbs) {
-            st[s].sub0 = c0 + (uint64_t)(wave - nt) * q * kSeg;
-            st[s].sub1 = st[s].sub0 + (uint64_t)q * kSeg;
-        } else if (BS == 2) {
-            // groups of JFSX_HYB_UR rows (a divisor of 32): every stream starts
-            // on a multiple of UR rows, so only the last row of a UR block can
-            // end a segment
-            constexpr uint32_t G = JFSX_HYB_UR;
-            const uint32_t ng = (uint32_t)((c1 - tt0 + 1024 * G - 1) / (1024 * G));
-            const uint32_t ra = G * (wave * ng / nt), rb = G * ((wave + 1) * ng / nt);
-            st[s].sub0 = tt0 + (uint64_t)ra * 1024;
-            st[s].sub1 = rb > ra ? (tt0 + (uint64_t)rb * 1024 < c1 ? tt0 + (uint64_t)rb * 1024 : c1) : st[s].sub0;
-        } else if (kRowSplit) {
-            const uint32_t ra = 2 * (v * npairs / V), rb = 2 * ((v + 1) * npairs / V);
-            st[s].sub0 = c0 + (uint64_t)ra * 1024;
-            st[s].sub1 = rb > ra ? (c0 + (uint64_t)rb * 1024 < c1 ? c0 + (uint64_t)rb * 1024 : c1) : st[s].sub0;
-        } else {
-            const uint32_t sa = v * nseg / V, sb = (v + 1) * nseg / V;
-            st[s].sub0 = c0 + (uint64_t)sa * kSeg;
-            st[s].sub1 = sb > sa ? (c0 + (uint64_t)sb * kSeg < c1 ? c0 + (uint64_t)sb * kSeg : c1) : st[s].sub0;
-        }
-        st[s].acc[0] = st[s].acc[1] = st[s].acc[2] = st[s].acc[3] = 0;
-        st[s].jlast = 0;
-        st[s].has = false;
-        st[s].A = 0;
-        st[s].lend = 0;
-        st[s].seg0 = c0 + (st[s].sub0 - c0) / kSeg * kSeg;  // start of the segment holding the stream's first row
-    }
-    // rows that are full for every non-empty stream: the fast path.  Empty
-    // streams (tasks with fewer segments than streams) alias stream 0's loads
-    // and skip every side effect (wave-uniform branch).
-    bool act[NS];
-    uint64_t rf = ~0ull, ld0[NS];
-#pragma unroll
-    for (int s = 0; s < NS; s++) {
-        act[s] = st[s].sub1 > st[s].sub0;
-        ld0[s] = act[s] ? st[s].sub0 : st[0].sub0;
-        if (act[s]) {
-            const uint64_t fr = (st[s].sub1 - st[s].sub0) / 1024;
-            rf = fr < rf ? fr : rf;
-        }
-    }
-    if (rf == ~0ull) rf = 0;
+    st.acc[0] = st.acc[1] = st.acc[2] = st.acc[3] = 0;
+    st.jlast = 0;
+    st.has = false;
+    st.A = 0;
+    st.lend = 0;
+    st.seg0 = c0 + (st.sub0 - c0) / kSeg * kSeg;  // start of the segment holding the stream's first row
+    // full rows of the stream: the fast path.  An empty stream (a task with
+    // fewer row pairs or segments than waves) has none.
+    // (the subtraction stands outside the select on purpose: inside it the
+    // compiler knows it cannot wrap, and every gcm_main_k schedules differently)
+    const bool act = st.sub1 > st.sub0;
+    const uint64_t fr = (st.sub1 - st.sub0) / 1024;
+    const uint64_t rf = act ? fr : 0;
+    const uint64_t ld0 = st.sub0;
     const uint8_t *src = blk.src;
     uint8_t *dst = blk.dst;
     const uint64_t lo = 16 * lane;
@@ -641,16 +571,16 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
     // BS: whole 32 KiB segments take their 32 rows of keystream from one
     // bitsliced AES pass (lane slot k = row k), then the rows stream through
     // XOR / store / GHASH / CRC with the keystream in registers.
-    if (BS && isbs && NS == 1 && act[0] && rf >= 32) {
+    if (BS && act && rf >= 32) {
         const uint64_t nfs = rf / 32;
         const uint32_t nrk[3] = {sch->c012[0], sch->c012[1], sch->c012[2]};
         const uint32_t rk3 = sch->rk[3];
         constexpr int PF = 4;  // rows of loads in flight
         uint4 pf[PF];
 #pragma unroll
-        for (int q = 0; q < PF; q++) pf[q] = ald16(src + ld0[0] + 1024 * q + lo);
+        for (int q = 0; q < PF; q++) pf[q] = ald16<kAeadNt>(src + ld0 + 1024 * q + lo);
         for (uint64_t sg = 0; sg < nfs; sg++) {
-            const uint64_t base = ld0[0] + (uint64_t)kSeg * sg;
+            const uint64_t base = ld0 + (uint64_t)kSeg * sg;
             uint32_t ks[128];
             jfsx_bs::ctr32(ks, nrk, rk3, (uint32_t)((base >> 4) + lane + 2),
                            [&](int r, int w) { return sch->bsu[r][w]; }, sch->r1c);
@@ -659,20 +589,18 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
             for (int k = 0; k < 32; k++) {
                 const uint4 d = pf[k % PF];
                 const uint64_t o = base + 1024 * k + lo;
-                if (k + PF < 32 || more) pf[k % PF] = ald16(src + o + 1024 * PF);
+                if (k + PF < 32 || more) pf[k % PF] = ald16<kAeadNt>(src + o + 1024 * PF);
                 const uint4 x = make_uint4(d.x ^ ks[k], d.y ^ ks[32 + k], d.z ^ ks[64 + k], d.w ^ ks[96 + k]);
                 const uint4 c = OPEN ? d : x, p = OPEN ? x : d;
-                ast16(dst + o, OPEN ? p : c);
+                ast16<kAeadNt>(dst + o, OPEN ? p : c);
                 const uint4 cq = crc_src<CRCMODE>(c, p);
-#ifndef JFSX_ABLATE_GHASH
-                ghash_step(lds, st[0].acc, gl, c);
-#endif
-                if (CRCMODE) st[0].A = crc_piece<kLdsCrc>(lds, st[0].A, cq.x, cq.y, cq.z, cq.w);
+                ghash_step(lds, st.acc, gl, c);
+                if (CRCMODE) st.A = crc_piece<kLdsCrc>(lds, st.A, cq.x, cq.y, cq.z, cq.w);
             }
             if (CRCMODE) {
-                crc_segment_done<CRCMODE>(blk, tab, lane, xl, st[0].seg0, st[0].A, false, lds, c0);
-                st[0].A = 0;
-                st[0].seg0 += kSeg;
+                crc_segment_done<CRCMODE>(blk, tab, lane, xl, st.seg0, st.A, false, lds, c0);
+                st.A = 0;
+                st.seg0 += kSeg;
             }
         }
         r0 = 32 * nfs;
@@ -683,52 +611,37 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
 #pragma unroll
     for (int i = 0; i < 60; i++) rk[i] = rk_load(sch->rk, i);
     uint32_t k1[4] = {sch->k1[0], sch->k1[1], sch->k1[2], sch->k1[3]};
-    uint4 nxt[NS];
-#pragma unroll
-    for (int s = 0; s < NS; s++)
-        nxt[s] = r0 < rf ? ald16(src + ld0[s] + 1024 * r0 + lo) : make_uint4(0, 0, 0, 0);
-#if JFSX_U2
-    // UR rows of one stream per iteration (2 in the 16-wave shape; the 8-wave
-    // shape has twice the VGPRs and takes JFSX_HYB_UR): the UR AES chains
-    // interleave, GHASH/CRC stay sequential (register peak of one row)
-    constexpr int UR = BS == 2 ? JFSX_HYB_UR : JFSX_UR0;
+    uint4 nxt = r0 < rf ? ald16<kAeadNt>(src + ld0 + 1024 * r0 + lo) : make_uint4(0, 0, 0, 0);
+    // UR rows per iteration (2 fits the 16-wave shape's 128 VGPRs): the UR AES
+    // chains interleave, GHASH/CRC stay sequential (register peak of one row)
+    constexpr int UR = 2;
     // the CRC's input is the loaded row itself: the plaintext in Seal, the
     // ciphertext (JFSX_CRC_CT) in Open
-    constexpr bool kL1 = KL1 > 0 && kRowSplit && JFSX_UCTR && CRCMODE != 0 && OPEN == ((CRCMODE & 4) != 0);
-    if (NS == 1 && act[0] && rf >= r0 + UR) {
+    constexpr bool kL1 = KL1 > 0 && kRowSplit && CRCMODE != 0 && OPEN == ((CRCMODE & 4) != 0);
+    if (act && rf >= r0 + UR) {
         uint4 nn[UR];
 #pragma unroll
-        for (int u = 0; u < UR; u++) nn[u] = ald16(src + ld0[0] + 1024 * (r0 + u) + lo);
-#if JFSX_UCTR
+        for (int u = 0; u < UR; u++) nn[u] = ald16<kAeadNt>(src + ld0 + 1024 * (r0 + u) + lo);
+        // counter-uniform terms of rounds 1-2 for a window of 64 values of the
+        // counter's upper 24 bits (aes_r2_uniform): lane l holds U = uw0 + l
         uint32_t uw[4] = {0, 0, 0, 0};
         uint32_t uw0 = 0;
         bool uwok = false;
-#endif
-        // task row index of the stream's first row: a multiple of 2 (16-wave
-        // shape, row pairs) or of UR (8-wave shape), so the compiler drops the
-        // segment-end test of rows that cannot end a segment
-        constexpr uint32_t RA = BS == 2 ? (32 % UR == 0 ? (uint32_t)UR : 1u) : 2u;
-        const uint32_t rb0 = (uint32_t)((ld0[0] - c0) >> 10) / RA * RA;
-        // software pipelining (8-wave shape, JFSX_HYB_SWP): the GHASH and CRC
-        // lookups of UR block i - 1 share a basic block with the AES of block
-        // i (independent LDS work to fill the rounds' latency); its segment
-        // end, if any, is handled after block i's stores
-        constexpr bool SWP = BS == 2 && JFSX_HYB_SWP;
-        static_assert(!SWP || 32 % UR == 0, "software pipelining needs UR | 32");
-        uint4 pc[UR], pq[UR];
-        bool pend = false;
-        uint32_t pr0 = 0;
+        // task row index of the stream's first row: a multiple of 2 (row
+        // pairs), so the compiler drops the segment-end test of the first row
+        // of a pair, which cannot end a segment
+        const uint32_t rb0 = (uint32_t)((ld0 - c0) >> 10) / 2u * 2u;
         const CrcL1Base l1g = kL1 ? crc_l1_base(tab.crc) : CrcL1Base{0, 0};
         for (; r0 + UR - 1 < rf; r0 += UR) {
             uint4 dd[UR];
 #pragma unroll
             for (int u = 0; u < UR; u++) dd[u] = nn[u];
-            const uint64_t o0 = ld0[0] + 1024 * r0 + lo;
+            const uint64_t o0 = ld0 + 1024 * r0 + lo;
             // (the L1 path prefetches after its last gather group, below: the
             // returns come in order, and a fold must not wait for HBM)
             if (!kL1 && r0 + 2 * UR - 1 < rf) {
 #pragma unroll
-                for (int u = 0; u < UR; u++) nn[u] = ald16(src + o0 + 1024 * (UR + u));
+                for (int u = 0; u < UR; u++) nn[u] = ald16<kAeadNt>(src + o0 + 1024 * (UR + u));
             }
             // UR * KL1 gathers in groups of LG terms of one row, one group per
             // AES round group; a group is folded into its row's crcL LLAG round
@@ -761,29 +674,19 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
                     } else if constexpr (S == LSTEPS) {
                         if (pre) {
 #pragma unroll
-                            for (int u = 0; u < UR; u++) nn[u] = ald16(src + o0 + 1024 * (UR + u));
+                            for (int u = 0; u < UR; u++) nn[u] = ald16<kAeadNt>(src + o0 + 1024 * (UR + u));
                         }
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
             };
-            if (SWP && pend) {
-#pragma unroll
-                for (int u = 0; u < UR; u++) {
-#ifndef JFSX_ABLATE_GHASH
-                    ghash_step(lds, st[0].acc, gl, pc[u]);
-#endif
-                    if (CRCMODE) st[0].A = crc_piece<kLdsCrc>(lds, st[0].A, pq[u].x, pq[u].y, pq[u].z, pq[u].w);
-                }
-            }
             uint32_t ctrs[UR];
 #pragma unroll
             for (int u = 0; u < UR; u++) ctrs[u] = (uint32_t)((o0 >> 4) + 2 + 64 * u);
             uint32_t ks2[UR][4];
-#if JFSX_UCTR
             {
                 // row counters C + 64 u (C = the first row's lane-0 counter, wave-uniform)
-                uint32_t C = (uint32_t)(((ld0[0] + 1024 * r0) >> 4) + 2);
+                uint32_t C = (uint32_t)(((ld0 + 1024 * r0) >> 4) + 2);
                 OPAQUE(C);
                 // the window must hold U(C) .. U(C + 64 UR - 1 + 1)
                 if (!uwok || (C >> 8) < uw0 || ((C + 64u * UR + 63u) >> 8) - uw0 > 63u) {
@@ -806,151 +709,110 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
                 }
                 aes_ctr_blocks_u<UR>(lds, loff, rk, k1, ctrs, u2, d2, cym, ks2, side);
             }
-#else
-            aes_ctr_blocks<UR>(lds, loff, rk, k1, ctrs, ks2);
-#endif
 #pragma unroll
             for (int u = 0; u < UR; u++) {
                 const uint64_t o = o0 + 1024 * u;
-#if JFSX_UCTR
                 // data ^ keystream ^ last round key in one v_bitop3
                 const uint4 x = make_uint4(xor3(dd[u].x, ks2[u][0], rk[56]), xor3(dd[u].y, ks2[u][1], rk[57]),
                                            xor3(dd[u].z, ks2[u][2], rk[58]), xor3(dd[u].w, ks2[u][3], rk[59]));
-#else
-                const uint4 x = make_uint4(dd[u].x ^ ks2[u][0], dd[u].y ^ ks2[u][1], dd[u].z ^ ks2[u][2],
-                                           dd[u].w ^ ks2[u][3]);
-#endif
                 const uint4 c = OPEN ? dd[u] : x, p = OPEN ? x : dd[u];
-                ast16(dst + o, OPEN ? p : c);
+                ast16<kAeadNt>(dst + o, OPEN ? p : c);
                 const uint4 cq = crc_src<CRCMODE>(c, p);
-                if (SWP) {
-                    pc[u] = c;
-                    pq[u] = cq;
-                    continue;
-                }
-#ifndef JFSX_ABLATE_GHASH
-                ghash_step(lds, st[0].acc, gl, c);
-#endif
+                ghash_step(lds, st.acc, gl, c);
                 if constexpr (kL1)
-                    st[0].A = crc_piece_l1<kLdsCrc, (kL1 ? KL1 : 4)>(lds, st[0].A, cq.x, cq.y, cq.z, cq.w, crcL[u]);
+                    st.A = crc_piece_l1<kLdsCrc, (kL1 ? KL1 : 4)>(lds, st.A, cq.x, cq.y, cq.z, cq.w, crcL[u]);
                 else if (CRCMODE)
-                    st[0].A = crc_piece<kLdsCrc>(lds, st[0].A, cq.x, cq.y, cq.z, cq.w);
+                    st.A = crc_piece<kLdsCrc>(lds, st.A, cq.x, cq.y, cq.z, cq.w);
                 if (CRCMODE && ((rb0 + (uint32_t)r0 + u) & 31) == 31) {
-                    crc_segment_done<CRCMODE>(blk, tab, lane, xl, st[0].seg0, st[0].A, st[0].seg0 < st[0].sub0, lds,
-                                              c0);
-                    st[0].A = 0;
-                    st[0].seg0 += kSeg;
+                    crc_segment_done<CRCMODE>(blk, tab, lane, xl, st.seg0, st.A, st.seg0 < st.sub0, lds, c0);
+                    st.A = 0;
+                    st.seg0 += kSeg;
                 }
             }
-            if (SWP) {
-                // the previous block's segment end (its CRC went in above)
-                if (CRCMODE && pend && ((rb0 + pr0 + UR - 1) & 31) == 31) {
-                    crc_segment_done<CRCMODE>(blk, tab, lane, xl, st[0].seg0, st[0].A, st[0].seg0 < st[0].sub0, lds,
-                                              c0);
-                    st[0].A = 0;
-                    st[0].seg0 += kSeg;
-                }
-                pend = true;
-                pr0 = (uint32_t)r0;
-            }
         }
-        if (SWP && pend) {
-#pragma unroll
-            for (int u = 0; u < UR; u++) {
-#ifndef JFSX_ABLATE_GHASH
-                ghash_step(lds, st[0].acc, gl, pc[u]);
-#endif
-                if (CRCMODE) st[0].A = crc_piece<kLdsCrc>(lds, st[0].A, pq[u].x, pq[u].y, pq[u].z, pq[u].w);
-            }
-            if (CRCMODE && ((rb0 + pr0 + UR - 1) & 31) == 31) {
-                crc_segment_done<CRCMODE>(blk, tab, lane, xl, st[0].seg0, st[0].A, st[0].seg0 < st[0].sub0, lds, c0);
-                st[0].A = 0;
-                st[0].seg0 += kSeg;
-            }
-        }
-        if (r0 < rf) nxt[0] = ald16(src + ld0[0] + 1024 * r0 + lo);
+        if (r0 < rf) nxt = ald16<kAeadNt>(src + ld0 + 1024 * r0 + lo);
     }
-#endif
+    // The rows left over, one at a time.  From here to the end of the stream
+    // epilogue the steps keep the form of loops over the wave's streams, of
+    // which there is one (s < 1): the compiler derives its block layout and
+    // the whole kernel's register allocation from that form, and flattening
+    // them changes every gcm_main_k's instruction stream
+    // (profiles/r8/retire/README.md), which then wants a same-box A/B.
     for (uint64_t r = r0; r < rf; r++) {
-        uint4 d[NS];
-        uint32_t ctr[NS];
+        uint4 d[1];
+        uint32_t ctr[1];
 #pragma unroll
-        for (int s = 0; s < NS; s++) {
-            d[s] = nxt[s];
-            const uint64_t o = ld0[s] + 1024 * r + lo;
-            if (r + 1 < rf) nxt[s] = ald16(src + o + 1024);
+        for (int s = 0; s < 1; s++) {
+            d[s] = nxt;
+            const uint64_t o = ld0 + 1024 * r + lo;
+            if (r + 1 < rf) nxt = ald16<kAeadNt>(src + o + 1024);
             ctr[s] = (uint32_t)((o >> 4) + 2);
         }
-        uint32_t ks[NS][4];
-        aes_ctr_blocks<NS>(lds, loff, rk, k1, ctr, ks);
+        uint32_t ks[1][4];
+        aes_ctr_blocks<1>(lds, loff, rk, k1, ctr, ks);
 #pragma unroll
-        for (int s = 0; s < NS; s++) {
-            if (!act[s]) continue;
-            const uint64_t o = st[s].sub0 + 1024 * r + lo;
+        for (int s = 0; s < 1; s++) {
+            if (!act) continue;
+            const uint64_t o = st.sub0 + 1024 * r + lo;
             const uint4 x = make_uint4(d[s].x ^ ks[s][0], d[s].y ^ ks[s][1], d[s].z ^ ks[s][2], d[s].w ^ ks[s][3]);
             const uint4 c = OPEN ? d[s] : x, p = OPEN ? x : d[s];
-            ast16(dst + o, OPEN ? p : c);
+            ast16<kAeadNt>(dst + o, OPEN ? p : c);
             const uint4 cq = crc_src<CRCMODE>(c, p);
-            ghash_step(lds, st[s].acc, gl, c);
-            if (CRCMODE) st[s].A = crc_piece<kLdsCrc>(lds, st[s].A, cq.x, cq.y, cq.z, cq.w);
+            ghash_step(lds, st.acc, gl, c);
+            if (CRCMODE) st.A = crc_piece<kLdsCrc>(lds, st.A, cq.x, cq.y, cq.z, cq.w);
         }
-        if (CRCMODE && ((uint32_t)((ld0[0] - c0) >> 10) + (uint32_t)r & 31) == 31) {
-            // (NS > 1 only with the segment split: every stream starts on a segment)
-#pragma unroll
-            for (int s = 0; s < NS; s++) {
-                if (!act[s]) continue;
-                crc_segment_done<CRCMODE>(blk, tab, lane, xl, st[s].seg0, st[s].A, st[s].seg0 < st[s].sub0, lds, c0);
-                st[s].A = 0;
-                st[s].seg0 += kSeg;
+        if (CRCMODE && ((uint32_t)((ld0 - c0) >> 10) + (uint32_t)r & 31) == 31) {
+            if (act) {
+                crc_segment_done<CRCMODE>(blk, tab, lane, xl, st.seg0, st.A, st.seg0 < st.sub0, lds, c0);
+                st.A = 0;
+                st.seg0 += kSeg;
             }
         }
     }
 #pragma unroll
-    for (int s = 0; s < NS; s++) {
-        if (rf && act[s]) {
-            st[s].has = true;
-            st[s].jlast = (st[s].sub0 + 1024 * (rf - 1) + lo) >> 4;
+    for (int s = 0; s < 1; s++) {
+        if (rf && act) {
+            st.has = true;
+            st.jlast = (st.sub0 + 1024 * (rf - 1) + lo) >> 4;
         }
         // lanes whose last piece lies in the last full row: their CRC shift to
         // a segment end starts at that row's end (lend == 0, crc_segment_end)
-        const uint64_t tailRef = st[s].sub0 + 1024 * rf;
-        // ragged remainder of this stream (block tail or unequal streams)
-        for (uint64_t row = tailRef; row < st[s].sub1; row += 1024)
-            st[s] = row_generic<OPEN, CRCMODE>(lds, loff, gl, sch, blk, tab, lane, xl, st[s], row, c0, c1);
+        const uint64_t tailRef = st.sub0 + 1024 * rf;
+        // ragged remainder of this stream (block tail)
+        for (uint64_t row = tailRef; row < st.sub1; row += 1024)
+            st = row_generic<OPEN, CRCMODE>(lds, loff, gl, sch, blk, tab, lane, xl, st, row, c0, c1);
         // a stream that ended inside a segment still owes that segment's CRC
         // (or, when another wave holds the rest of the segment, its share)
-        if (CRCMODE && act[s] && st[s].seg0 < st[s].sub1) {
-            const uint64_t seg1 = st[s].seg0 + kSeg < c1 ? st[s].seg0 + kSeg : c1;
-            crc_segment_end<CRCMODE>(blk, tab, lane, xl, st[s].seg0, seg1, st[s].A, st[s].lend, tailRef,
-                                     st[s].seg0 < st[s].sub0 || st[s].sub1 < seg1, lds,
-                                     (uint32_t)((st[s].seg0 - c0) / kSeg));
-            st[s].seg0 = st[s].sub1;
+        if (CRCMODE && act && st.seg0 < st.sub1) {
+            const uint64_t seg1 = st.seg0 + kSeg < c1 ? st.seg0 + kSeg : c1;
+            crc_segment_end<CRCMODE>(blk, tab, lane, xl, st.seg0, seg1, st.A, st.lend, tailRef,
+                                     st.seg0 < st.sub0 || st.sub1 < seg1, lds, (uint32_t)((st.seg0 - c0) / kSeg));
+            st.seg0 = st.sub1;
         }
     }
 
     MAIN_STAMP(first_task, 3);
-    // ---- stream epilogues: lift lane accumulators to the stream end, reduce ----
+    // ---- stream epilogue: lift lane accumulators to the stream end, reduce ----
     const uint64_t nblk = (blk.len + 15) >> 4;
 #pragma unroll
-    for (int s = 0; s < NS; s++) {
-        const uint64_t wend = (st[s].sub1 + 15) >> 4;  // blocks before the stream end
+    for (int s = 0; s < 1; s++) {
+        const uint64_t wend = (st.sub1 + 15) >> 4;  // blocks before the stream end
         g128 z = {{0, 0, 0, 0}};
-        if (st[s].has && st[s].sub1 > st[s].sub0) {
-            const uint32_t e = (uint32_t)(wend + 1 - st[s].jlast);  // in [2, 65]
+        if (st.has && st.sub1 > st.sub0) {
+            const uint32_t e = (uint32_t)(wend + 1 - st.jlast);  // in [2, 65]
             uint32_t a[4];
-            gh_rho_inv(st[s].acc, gl, a);
+            gh_rho_inv(st.acc, gl, a);
 #ifdef JFSX_ABLATE_LIFT
             z = g_from_mem(a);  // timing experiment only: wrong tags
 #else
-            z = JFSX_GF_CT_LIFT ? g_mul_ct_call(g_from_mem(a), g_from_mem(sch->hpow[e]))
-                                : g_mul(g_from_mem(a), g_from_mem(sch->hpow[e]));
+            z = g_mul_ct_call(g_from_mem(a), g_from_mem(sch->hpow[e]));
 #endif
         }
         uint32_t zm[4];
         g_to_mem(z, zm);
         for (int k = 0; k < 4; k++) zm[k] = wave_xor(zm[k]);
         if (lane == 0) {
-            const uint32_t slot = task.slot0 + wave * NS + s;
+            const uint32_t slot = task.slot0 + wave;
             partial[4 * slot + 0] = zm[0];
             partial[4 * slot + 1] = zm[1];
             partial[4 * slot + 2] = zm[2];
@@ -958,8 +820,7 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
             pexp[slot] = (uint32_t)(nblk - wend);
             // the 8-wave bitsliced shape leaves the upper half of the task's
             // kSlotsPerTask slots unused: zero them for gcm_finalize
-            for (uint32_t u = task.slot0 + GcmShape<BS>::waves * NS + wave * NS + s; u < task.slot0 + kSlotsPerTask;
-                 u += GcmShape<BS>::waves * NS) {
+            for (uint32_t u = task.slot0 + V + wave; u < task.slot0 + kSlotsPerTask; u += V) {
                 partial[4 * u + 0] = partial[4 * u + 1] = partial[4 * u + 2] = partial[4 * u + 3] = 0;
                 pexp[u] = 0;
             }
@@ -980,7 +841,7 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
 #endif
     MAIN_STAMP(first_task, 4);
     // ---- segments shared by two or more waves: sum the raw shares, finish ----
-    if (CRCMODE && kShares) {
+    if (CRCMODE && kRowSplit) {
         __syncthreads();
         if (wave == 0) {
             const uint32_t *raw = reinterpret_cast<const uint32_t *>(lds + kLdsSegRaw);
@@ -1011,13 +872,13 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
 // dispatched in order, round-robin over the XCDs, and the next one waits for
 // a CU of its own XCD (measured with the TRACE variant on configs[4]'s
 // 64 KiB-4 MiB blocks: CUs 79 % busy, 115 us mean gap between tasks).
-template <bool OPEN, int CRCMODE, int NS, int BS, int KL1 = 0>
+template <bool OPEN, int CRCMODE, bool BS, int KL1 = 0>
 __global__ __launch_bounds__(GcmShape<BS>::threads) void gcm_main_k(const Task *__restrict__ tasks, uint32_t ntasks,
                                                        uint32_t *__restrict__ queue,
                                                        const BlkDev *__restrict__ blks,
                                                        const GcmSched *__restrict__ sched,
                                                        uint32_t *__restrict__ partial, uint32_t *__restrict__ pexp,
-                                                       DevTables tab, uint32_t hyb) {
+                                                       DevTables tab) {
     __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
     __shared__ uint32_t s_task;
     const uint32_t tid = threadIdx.x;
@@ -1046,15 +907,6 @@ __global__ __launch_bounds__(GcmShape<BS>::threads) void gcm_main_k(const Task *
     const uint32_t loff = ((lane & 31) << 2) | 0x00010000u;  // AES replica offset | table base
     const GhLane gl = gh_lane(lane);
     const uint32_t xl = CRCMODE ? tab.crcx[lane] : 0u;
-    if (BS == 2 && wave < GcmShape<BS>::waves - hyb_nbs(hyb)) {
-        // the T-table waves win VALU arbitration against the bitsliced ones
-        switch ((hyb >> 16) & 3u) {
-            case 1: __builtin_amdgcn_s_setprio(1); break;
-            case 2: __builtin_amdgcn_s_setprio(2); break;
-            case 3: __builtin_amdgcn_s_setprio(3); break;
-            default: break;
-        }
-    }
     if (tid == 0) s_task = atomicAdd(queue, 1u);
     for (;;) {
         // also orders this task's table writes after the previous task's readers
@@ -1063,8 +915,8 @@ __global__ __launch_bounds__(GcmShape<BS>::threads) void gcm_main_k(const Task *
         if (ti >= ntasks) break;  // the same for every wave: the queue is exhausted
         __syncthreads();          // every wave holds ti: s_task may take the next index
         if (tid == 0) s_task = atomicAdd(queue, 1u);  // the next task's index arrives during this one
-        gcm_task<OPEN, CRCMODE, NS, BS, KL1>(lds, tasks[ti], blks, sched, partial, pexp, tab, tid, wave, lane, loff, gl,
-                                        xl, hyb);
+        gcm_task<OPEN, CRCMODE, BS, KL1>(lds, tasks[ti], blks, sched, partial, pexp, tab, tid, wave, lane, loff, gl,
+                                         xl);
     }
 }
 
@@ -1100,82 +952,6 @@ __device__ void aes_enc_global(const uint32_t *aes, const uint32_t *rk, const ui
         out[c] = (gS(aes, a & 0xff) | (gS(aes, (b >> 8) & 0xff) << 8) | (gS(aes, (cc >> 16) & 0xff) << 16) |
                   (gS(aes, d >> 24) << 24)) ^ rk[56 + c];
     }
-}
-
-// z = x * y in GF(2^128) for a wave-uniform y and a per-lane x, four bits of
-// x per step (Horner from the high coefficients: z = z x^4 + y N_t), the 16
-// multiples y (n3 + n2 x + n1 x^2 + n0 x^3) in LDS.  About 600 instructions
-// against g_mul's 2000; every lane of the wave must call it (barriers).
-// JFSX_GF_CT (default 1): keysetup's and finalize's GF products by
-// integer multiplies (g_mul_ct, jfsx_gf.h) instead of LDS nibble tables
-#ifndef JFSX_GF_CT
-#define JFSX_GF_CT 1
-#endif
-#ifndef JFSX_KS_NIB
-#define JFSX_KS_NIB 1  // 0: keysetup with the bit-serial g_mul (A/B)
-#endif
-__device__ __forceinline__ g128 g_mul_uy(const g128 &x, const g128 &y, uint4 *M, uint32_t lane) {
-    const g128 y1 = g_mulx(y), y2 = g_mulx(y1), y3 = g_mulx(y2);
-    __syncthreads();  // the previous call's readers are done with M
-    if (lane < 16) {
-        uint32_t m[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            m[k] = ((lane & 8) ? y.w[k] : 0u) ^ ((lane & 4) ? y1.w[k] : 0u) ^ ((lane & 2) ? y2.w[k] : 0u) ^
-                   ((lane & 1) ? y3.w[k] : 0u);
-        M[lane] = make_uint4(m[0], m[1], m[2], m[3]);
-    }
-    __syncthreads();
-    g128 z = {{0, 0, 0, 0}};
-#pragma unroll 4
-    for (int t = 31; t >= 0; t--) {
-        // z x^4: the four coefficients shifted out (low bits of w[3]) fold
-        // back as in four g_mulx steps
-        const uint32_t sh = z.w[3] & 15u;
-        z.w[3] = __builtin_amdgcn_alignbit(z.w[2], z.w[3], 4);
-        z.w[2] = __builtin_amdgcn_alignbit(z.w[1], z.w[2], 4);
-        z.w[1] = __builtin_amdgcn_alignbit(z.w[0], z.w[1], 4);
-        z.w[0] = (z.w[0] >> 4) ^ ((sh & 1u) ? 0xE1000000u >> 3 : 0u) ^ ((sh & 2u) ? 0xE1000000u >> 2 : 0u) ^
-                 ((sh & 4u) ? 0xE1000000u >> 1 : 0u) ^ ((sh & 8u) ? 0xE1000000u : 0u);
-        const uint32_t n = (x.w[t >> 3] >> (28 - 4 * (t & 7))) & 15u;
-        const uint4 mv = M[n];
-        z.w[0] ^= mv.x, z.w[1] ^= mv.y, z.w[2] ^= mv.z, z.w[3] ^= mv.w;
-    }
-    return z;
-}
-
-// g_mul_uy for a one-wave kernel (keysetup): the 32 table rows x selects are
-// loaded before the Horner chain starts (they depend on x alone), so the
-// chain is VALU work only instead of one dependent LDS round trip per step.
-// Holds the rows in 128 VGPRs -- fine in keysetup's 64-thread workgroup, not
-// in the 1024-thread finalize, which keeps g_mul_uy.
-__device__ __forceinline__ g128 g_mul_uy_pre(const g128 &x, const g128 &y, uint4 *M, uint32_t lane) {
-    const g128 y1 = g_mulx(y), y2 = g_mulx(y1), y3 = g_mulx(y2);
-    __syncthreads();  // the previous call's readers are done with M
-    if (lane < 16) {
-        uint32_t m[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            m[k] = ((lane & 8) ? y.w[k] : 0u) ^ ((lane & 4) ? y1.w[k] : 0u) ^ ((lane & 2) ? y2.w[k] : 0u) ^
-                   ((lane & 1) ? y3.w[k] : 0u);
-        M[lane] = make_uint4(m[0], m[1], m[2], m[3]);
-    }
-    __syncthreads();
-    uint4 mv[32];
-#pragma unroll
-    for (int t = 0; t < 32; t++) mv[t] = M[(x.w[t >> 3] >> (28 - 4 * (t & 7))) & 15u];
-    g128 z = {{0, 0, 0, 0}};
-#pragma unroll
-    for (int t = 31; t >= 0; t--) {
-        const uint32_t sh = z.w[3] & 15u;
-        z.w[3] = __builtin_amdgcn_alignbit(z.w[2], z.w[3], 4);
-        z.w[2] = __builtin_amdgcn_alignbit(z.w[1], z.w[2], 4);
-        z.w[1] = __builtin_amdgcn_alignbit(z.w[0], z.w[1], 4);
-        z.w[0] = (z.w[0] >> 4) ^ ((sh & 1u) ? 0xE1000000u >> 3 : 0u) ^ ((sh & 2u) ? 0xE1000000u >> 2 : 0u) ^
-                 ((sh & 4u) ? 0xE1000000u >> 1 : 0u) ^ ((sh & 8u) ? 0xE1000000u : 0u);
-        z.w[0] ^= mv[t].x, z.w[1] ^= mv[t].y, z.w[2] ^= mv[t].z, z.w[3] ^= mv[t].w;
-    }
-    return z;
 }
 
 // JFSX_KS_PHASES (a probe build, scripts/build_variant.sh): workgroup 0 of
@@ -1246,7 +1022,7 @@ __device__ __forceinline__ g128 g_mul_xpow(g128 v, uint32_t i) {
 // gcm_finalize_k reads h2k[k] only for bits its exponents have), the basis
 // x^i H^64 is one x^i product per lane (g_mul_xpow) instead of a 128-step
 // chain, and the bitsliced S-box masks are made only for a kernel that uses
-// them (need_bs: the bitsliced or hybrid main kernel).
+// them (need_bs: the bitsliced main kernel).
 __global__ __launch_bounds__(64) void gcm_keysetup_k(const KeyIn *__restrict__ keys, const BlkDev *__restrict__ blks,
                                                     GcmSched *__restrict__ sched, const uint32_t *__restrict__ gtab,
                                                     int need_bs) {
@@ -1354,17 +1130,15 @@ __global__ __launch_bounds__(64) void gcm_keysetup_k(const KeyIn *__restrict__ k
     }
     __syncthreads();
     KS_STAMP(5);
-#if JFSX_KS_NIB
     // H^e for e = lane (bits 0..5: six products by the uniform H^(2^q), each
     // kept where the lane's bit is set), then H^(64 + e) = H^e H^64, e < 4
-    __shared__ uint4 gM[16];
     {
         g128 z = {{0x80000000u, 0, 0, 0}};  // x^0 = 1
         for (int q = 0; q < 6; q++) {
-            const g128 m = JFSX_GF_CT ? g_mul_ct_call(z, hs[q]) : g_mul_uy_pre(z, hs[q], gM, lane);
+            const g128 m = g_mul_ct_call(z, hs[q]);
             if ((lane >> q) & 1) z = m;
         }
-        const g128 z64 = JFSX_GF_CT ? g_mul_ct_call(z, hs[6]) : g_mul_uy_pre(z, hs[6], gM, lane);
+        const g128 z64 = g_mul_ct_call(z, hs[6]);
         uint32_t m[4];
         g_to_mem(z, m);
         for (int q = 0; q < 4; q++) sc->hpow[lane][q] = m[q];
@@ -1373,19 +1147,6 @@ __global__ __launch_bounds__(64) void gcm_keysetup_k(const KeyIn *__restrict__ k
             for (int q = 0; q < 4; q++) sc->hpow[64 + lane][q] = m[q];
         }
     }
-#else
-    // H^e for e = lane and lane + 64 (< 68)
-    for (int rep = 0; rep < 2; rep++) {
-        const uint32_t e = lane + 64 * rep;
-        if (e >= 68) break;
-        g128 z = {{0x80000000u, 0, 0, 0}};  // x^0 = 1
-        for (int q = 0; q < 7; q++)
-            if ((e >> q) & 1) z = g_mul(z, hs[q]);
-        uint32_t m[4];
-        g_to_mem(z, m);
-        for (int q = 0; q < 4; q++) sc->hpow[e][q] = m[q];
-    }
-#endif
     KS_STAMP(6);
     // basis x^i H^64: i = lane, and i = lane + 64 as x^64 times that
     {
@@ -1401,11 +1162,7 @@ __global__ __launch_bounds__(64) void gcm_keysetup_k(const KeyIn *__restrict__ k
     {
         const uint64_t bits = blks[b].len * 8;
         g128 L = {{0, 0, (uint32_t)(bits >> 32), (uint32_t)bits}};
-#if JFSX_KS_NIB
-        const g128 LH = JFSX_GF_CT ? g_mul_ct_call(L, H) : g_mul_uy_pre(L, H, gM, lane);  // lane 0 stores
-#else
-        const g128 LH = lane == 0 ? g_mul(L, H) : L;
-#endif
+        const g128 LH = g_mul_ct_call(L, H);  // lane 0 stores
         if (lane == 0) {
             uint32_t m[4];
             g_to_mem(LH, m);
@@ -1428,22 +1185,19 @@ extern "C" int jfsx_debug_ks_phases(unsigned long long *out) {
 // finalize: one workgroup per block, one thread per partial slot
 // ---------------------------------------------------------------------------
 // Each slot's partial is lifted by H^e (e = pexp) as products by the powers
-// H^(2^k) the block's exponents use: per k, 16 threads build the 4-bit table
-// of that (block-uniform) power in LDS and every thread whose e has bit k set
-// takes the table product (g_mul_uy) -- 32 lookups instead of a bit-serial
-// 128-step product per set bit.  A small batch (the per-object path) has
-// blocks of many short tasks and so many slots: the workgroup grows to one
-// thread per slot (up to 1024) instead of one wave looping over them.
-// TH: the launch's thread cap.  TH = 64 (blocks of at most 64 slots: a group
-// of small per-object blocks) takes g_mul_uy_pre, whose table rows sit in
-// registers a 1024-thread workgroup does not have.
+// H^(2^k) the block's exponents use: per k, every thread whose e has bit k
+// set takes the integer-multiply product (g_mul_ct) by that block-uniform
+// power.  A small batch (the per-object path) has blocks of many short tasks
+// and so many slots: the workgroup grows to one thread per slot (up to 1024)
+// instead of one wave looping over them.
+// TH: the launch's thread cap (64 for blocks of at most 64 slots: a group of
+// small per-object blocks).
 template <bool OPEN, int CRCMODE, int TH>
 __global__ __launch_bounds__(TH) void gcm_finalize_k(const BlkDev *__restrict__ blks, const GcmSched *__restrict__ sched,
                                                       const uint32_t *__restrict__ partial,
                                                       const uint32_t *__restrict__ pexp, BlkOut *__restrict__ out) {
     const uint32_t b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthr = blockDim.x;
     const uint32_t nw = nthr >> 6;
-    __shared__ uint4 M[16];
     __shared__ uint32_t sor[16];
     __shared__ uint32_t sred[16][4];
     __shared__ uint32_t h2k[32][4];  // the block's H^(2^k), staged once (not a global load per product)
@@ -1470,9 +1224,7 @@ __global__ __launch_bounds__(TH) void gcm_finalize_k(const BlkDev *__restrict__ 
         g128 z = g_from_mem(m);
         for (int k = 0; k < 32 && (eo >> k); k++) {
             if (!((eo >> k) & 1u)) continue;
-            const g128 zk = JFSX_GF_CT ? g_mul_ct_call(z, g_from_mem(h2k[k]))
-                            : TH == 64 ? g_mul_uy_pre(z, g_from_mem(h2k[k]), M, tid)
-                                       : g_mul_uy(z, g_from_mem(h2k[k]), M, tid);
+            const g128 zk = g_mul_ct_call(z, g_from_mem(h2k[k]));
             if ((e >> k) & 1u) z = zk;
         }
         g_to_mem(z, m);
@@ -1510,14 +1262,13 @@ __global__ __launch_bounds__(TH) void gcm_finalize_k(const BlkDev *__restrict__ 
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-// need_bs: the bitsliced main kernel runs (JFSX_CTX_BITSLICE, or the hybrid
-// shape selected by JFSX_GCM_HYBRID), so the schedule carries its S-box masks
+// need_bs: the bitsliced main kernel runs (JFSX_CTX_BITSLICE), so the
+// schedule carries its S-box masks
 void launch_gcm_keysetup(hipStream_t s, int n, const KeyIn *keys, const BlkDev *blks, GcmSched *sched, DevTables t,
                          bool bitslice) {
-    static const bool hybrid = getenv("JFSX_GCM_HYBRID") != nullptr;
     if (n > 0)
         hipLaunchKernelGGL(gcm_keysetup_k, dim3(n), dim3(64), 0, s, keys, blks, sched, t.aes,
-                           (int)(bitslice || hybrid));
+                           (int)bitslice);
 }
 
 // crc_l1: the 16-wave T-table kernel takes JFSX_CRC_L1K of the fused CRC's
@@ -1529,29 +1280,18 @@ void launch_gcm_main(hipStream_t s, int ntasks, int ncu, uint32_t *queue, bool o
     if (ntasks <= 0) return;
     const unsigned grid = (unsigned)(ntasks < ncu ? ntasks : ncu);  // persistent: one workgroup per CU
     // queue: zeroed by the caller (uploaded with the batch descriptors)
-    // JFSX_GCM_HYBRID="nbs,rho,prio" selects the hybrid shape (BS = 2) for the
-    // T-table context (an A/B switch; see GcmShape)
-    static const uint32_t hyb = [] {
-        const char *e = getenv("JFSX_GCM_HYBRID");
-        unsigned nbs = 0, rho = 16, prio = 2;
-        if (!e || sscanf(e, "%u,%u,%u", &nbs, &rho, &prio) < 1) return 0xffffffffu;
-        return (nbs & 7u) | ((rho & 255u) << 8) | ((prio & 3u) << 16);
-    }();
 #define L(O, C)                                                                                              \
     do {                                                                                                     \
         if (bitslice)                                                                                        \
-            hipLaunchKernelGGL((gcm_main_k<O, C, 1, 1>), dim3(grid), dim3(GcmShape<1>::threads), 0, s, tasks,    \
-                               (uint32_t)ntasks, queue, blks, sched, partial, pexp, t, 0u);                  \
-        else if (hyb != 0xffffffffu)                                                                         \
-            hipLaunchKernelGGL((gcm_main_k<O, C, 1, 2>), dim3(grid), dim3(GcmShape<2>::threads), 0, s, tasks,    \
-                               (uint32_t)ntasks, queue, blks, sched, partial, pexp, t, hyb);                 \
+            hipLaunchKernelGGL((gcm_main_k<O, C, true>), dim3(grid), dim3(GcmShape<true>::threads), 0, s, tasks, \
+                               (uint32_t)ntasks, queue, blks, sched, partial, pexp, t);                      \
         else if (crc_l1 && (C) != 0 && (O) == (((C) & 4) != 0))                                              \
-            hipLaunchKernelGGL((gcm_main_k<O, C, kStreams, 0, ((C) != 0 && (O) == (((C) & 4) != 0)) ? JFSX_CRC_L1K : 0>), \
-                               dim3(grid), dim3(GcmShape<0>::threads), 0, s, tasks, (uint32_t)ntasks, queue, blks,  \
-                               sched, partial, pexp, t, 0u);                                                 \
+            hipLaunchKernelGGL((gcm_main_k<O, C, false, ((C) != 0 && (O) == (((C) & 4) != 0)) ? JFSX_CRC_L1K : 0>), \
+                               dim3(grid), dim3(GcmShape<false>::threads), 0, s, tasks, (uint32_t)ntasks, queue, blks, \
+                               sched, partial, pexp, t);                                                     \
         else                                                                                                 \
-            hipLaunchKernelGGL((gcm_main_k<O, C, kStreams, 0>), dim3(grid), dim3(GcmShape<0>::threads), 0, s,    \
-                               tasks, (uint32_t)ntasks, queue, blks, sched, partial, pexp, t, 0u);           \
+            hipLaunchKernelGGL((gcm_main_k<O, C, false>), dim3(grid), dim3(GcmShape<false>::threads), 0, s,  \
+                               tasks, (uint32_t)ntasks, queue, blks, sched, partial, pexp, t);               \
     } while (0)
     switch ((open ? 8 : 0) | crc_mode) {
         case 8: L(true, 0); break;

@@ -21,49 +21,14 @@
 namespace jfsx {
 
 constexpr int kSeg = 32768;         // csBlock (disk_cache.go:1207)
-#ifndef JFSX_WAVES
-#define JFSX_WAVES 16
-#endif
-constexpr int kWaves = JFSX_WAVES;  // waves per transform workgroup
+constexpr int kWaves = 16;          // waves per transform workgroup
 constexpr int kThreads = kWaves * 64;
-#ifndef JFSX_STREAMS
-#define JFSX_STREAMS 1
-#endif
 // GHASH table walk issued in groups of lookups with a scheduling fence between
 // them (lower peak VGPRs): 4 = four quarters of 4, 1 = two halves of 8
 // (default; +0.7% over quarters at 8 GiB, equal at 64 GiB, fewer spills),
 // 0 = all 16 at once.
 #ifndef JFSX_GH8
 #define JFSX_GH8 1
-#endif
-// Two-row unrolled T-table loop (two AES chains interleaved); with the GHASH
-// quarters it fits the 128-VGPR cap (+2% measured).
-// rows per iteration of the default shape's T-table loop (2 fits 128 VGPRs)
-#ifndef JFSX_UR0
-#define JFSX_UR0 2
-#endif
-// rows per iteration of the 8-wave (BS = 2) shape's T-table loop
-#ifndef JFSX_HYB_UR
-#define JFSX_HYB_UR 4
-#endif
-// software-pipelined GHASH/CRC in the 8-wave shape's T-table loop
-#ifndef JFSX_HYB_SWP
-#define JFSX_HYB_SWP 0
-#endif
-#ifndef JFSX_U2
-#define JFSX_U2 1
-#endif
-// Counter-uniform rounds 1-2 in the two-row loop (aes_r2_uniform, jfsx_gcm.hip).
-#ifndef JFSX_UCTR
-#define JFSX_UCTR 1
-#endif
-// GHASH accumulator rotation (gh_rho) by v_perm selectors instead of v_cndmask.
-#ifndef JFSX_GHPERM
-#define JFSX_GHPERM 1
-#endif
-// CRC table addresses by an SDWA byte-select shift (byte_x4, jfsx_dev.h).
-#ifndef JFSX_CRCSDWA
-#define JFSX_CRCSDWA 1
 #endif
 // Fused CRC in the 16-wave GCM kernel: K of the step's 12 data-only slice
 // lookups through the vector L1 (4, 8 or 12; crc_piece_l1, jfsx_dev.h), issued
@@ -82,12 +47,7 @@ constexpr int kThreads = kWaves * 64;
 #ifndef JFSX_CRC_L1_DEFAULT
 #define JFSX_CRC_L1_DEFAULT 1
 #endif
-// T-table rounds 2..13 with pre-rotated round keys folded into a v_bitop3 (AES_COL).
-#ifndef JFSX_RKR
-#define JFSX_RKR 1
-#endif
-constexpr int kStreams = JFSX_STREAMS;        // independent segment streams per wave (ILP)
-constexpr int kSlotsPerTask = kWaves * kStreams;  // GHASH/Poly partial slots per task
+constexpr int kSlotsPerTask = kWaves;  // GHASH/Poly partial slots per task (one stream per wave)
 constexpr int kMaxTaskBytes = 4 << 20;
 constexpr uint32_t kCrcPoly = 0x82F63B78u;  // reflected Castagnoli
 
@@ -200,7 +160,7 @@ __device__ __forceinline__ g128 g_mulx(g128 v) {
 }
 
 // per-lane x times per-lane y from integer multiplies (jfsx_gf.h): about 500
-// instructions against g_mul's 2000, no LDS, no barrier
+// instructions, no LDS, no barrier
 __device__ __forceinline__ g128 g_mul_ct(const g128 &x, const g128 &y) {
     g128 z;
     jfsx_gf::mul(x.w, y.w, z.w);
@@ -210,27 +170,6 @@ __device__ __forceinline__ g128 g_mul_ct(const g128 &x, const g128 &y) {
 // the same as a call: the GCM kernels take it this way (inlined into them,
 // the iterative-ILP scheduler of the ROCm 7.2 compiler crashes)
 __device__ __noinline__ g128 g_mul_ct_call(g128 x, g128 y) { return g_mul_ct(x, y); }
-
-// generic bit-serial product (SP 800-38D Algorithm 1)
-__device__ __noinline__ g128 g_mul(g128 x, g128 y) {
-    g128 z = {{0, 0, 0, 0}};
-    g128 v = y;
-#pragma unroll 1
-    for (int k = 0; k < 4; k++) {
-        uint32_t xw = x.w[k];
-#pragma unroll 8
-        for (int i = 0; i < 32; i++) {
-            uint32_t m = 0u - (xw >> 31);
-            xw <<= 1;
-            z.w[0] ^= v.w[0] & m;
-            z.w[1] ^= v.w[1] & m;
-            z.w[2] ^= v.w[2] & m;
-            z.w[3] ^= v.w[3] & m;
-            v = g_mulx(v);
-        }
-    }
-    return z;
-}
 
 // spread the low 16 bits of x to the even bit positions
 __device__ __forceinline__ uint32_t spread16(uint32_t x) {

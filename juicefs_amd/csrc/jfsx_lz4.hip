@@ -36,12 +36,6 @@
 
 #include "jfsx_dev.h"
 
-// TabL::put as one masked LDS write (ds_mskor_b32) instead of an and / or
-// atomic pair; -DJFSX_LZ4_MSKOR=0 builds the pair (A/B)
-#ifndef JFSX_LZ4_MSKOR
-#define JFSX_LZ4_MSKOR 1
-#endif
-
 namespace jfsx {
 
 namespace {
@@ -331,16 +325,11 @@ struct TabL {
     __device__ __forceinline__ void put(uint32_t h, uint32_t v) const {
         lo[h] = (uint16_t)v;
         const uint32_t sh = 2 * (h & 15);
-#if JFSX_LZ4_MSKOR
         // one LDS op: word = (word & ~mask) | bits (ds_mskor_b32, atomic in
         // LDS like the and / or pair it replaces; a wave's LDS ops complete
         // in order, so a later read of the word sees it)
         const uint32_t a = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)&hb[h >> 4];
         asm volatile("ds_mskor_b32 %0, %1, %2" ::"v"(a), "v"(3u << sh), "v"(((v >> 16) & 3u) << sh) : "memory");
-#else
-        atomicAnd(&hb[h >> 4], ~(3u << sh));
-        atomicOr(&hb[h >> 4], ((v >> 16) & 3u) << sh);
-#endif
     }
     __device__ void sweep(uint32_t s, uint32_t lane) {
         // lane owns words 4 lane .. 4 lane + 3 and their 64 entries
@@ -370,9 +359,7 @@ struct TabL {
 
 // One wave per block.  ZDev.len = input bytes, ZDev.cap >= LZ4_compressBound
 // (checked on the host); ZOut.out_len = compressed bytes.
-#ifndef JFSX_LZ4_K0
-#define JFSX_LZ4_K0 4
-#endif
+constexpr uint32_t kLz4K0 = 4;  // lanes of the first search step after a match
 template <class Tab>
 __device__ __forceinline__ void lz4c_block(Tab &T, const uint8_t *src, uint8_t *dst, const uint32_t n,
                                            const Img &I, const bool small, const uint32_t lane, ZOut *out) {
@@ -398,11 +385,11 @@ __device__ __forceinline__ void lz4c_block(Tab &T, const uint8_t *src, uint8_t *
                 if (!iwin_has(W, I, anchor, q0 - anchor + 72)) iwin_load(W, I, anchor, lane);
                 // speculation width: a step runs the next K probes (a prefix of
                 // the serial search, so the output is unchanged); a search
-                // starts with JFSX_LZ4_K0 lanes and doubles K on each step
+                // starts with kLz4K0 lanes and doubles K on each step
                 // without a match -- on text the first match comes within a few
                 // probes, and every probe costs a random table read and a random
                 // candidate read
-                uint32_t K = JFSX_LZ4_K0;
+                uint32_t K = kLz4K0;
                 for (uint32_t k0 = 0;; k0 += K, K = K < 32 ? 2 * K : 64) {
                     const uint32_t k = k0 + lane;
                     const uint32_t p = q0 + probe_off(k);
@@ -686,10 +673,7 @@ typedef __attribute__((address_space(1))) v4u gv4u;
 // memory in coalesced 16-byte stores (one 1 KiB wave store per step).  Output
 // position p sits at ring[(p + s) & (R - 1)], s = dst & 15, so a ring slot and
 // the global address of its byte agree modulo 16.
-#ifndef JFSX_LZ4_RING
-#define JFSX_LZ4_RING 8192
-#endif
-constexpr uint32_t kDRing = JFSX_LZ4_RING;  // decoder ring: the most recent output bytes
+constexpr uint32_t kDRing = 8192;  // decoder ring: the most recent output bytes
 #ifndef JFSX_LZ4_FLUSH
 #define JFSX_LZ4_FLUSH 4096
 #endif
@@ -883,14 +867,10 @@ __global__ __launch_bounds__(64) void lz4_decompress_k(const ZDev *__restrict__ 
                             ring[dp & RM] = ring[(dp - off) & RM];
 #endif
                         } else {
-#ifdef JFSX_ABLATE_FAR
-                            ring[dp & RM] = (uint8_t)off;
-#else
                             // farther back than the ring: flushed, read dst
                             const uint32_t srcp = op + ll - off;
                             fence(srcp + 64u);
                             ring[dp & RM] = (uint8_t)ld8(dst + srcp + lane);
-#endif
                         }
                         op += __builtin_amdgcn_readlane(cand.tot, kk);
                         kk = (info >> 8) & 63u;
@@ -984,13 +964,9 @@ __global__ __launch_bounds__(64) void lz4_decompress_k(const ZDev *__restrict__ 
                 }
             } else if (ml <= 64 && ml <= off) {
                 // disjoint and farther back than the ring: flushed, read dst
-#ifdef JFSX_ABLATE_FAR
-                if (lane < ml) ring[(op + s + lane) & RM] = (uint8_t)off;
-#else
                 if (op - off + ml > fl) flush_all();
                 fence(op - off + ml);
                 if (lane < ml) ring[(op + s + lane) & RM] = (uint8_t)ld8(dst + op - off + lane);
-#endif
             } else if (off != 0 && off <= 64 && ml <= R && ml <= (1u << 24)) {
                 // short period: the off source bytes, read once, repeat.  j % off
                 // by a float reciprocal (j < 2^24: the quotient is off by at most one)

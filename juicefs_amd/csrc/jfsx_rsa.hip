@@ -32,10 +32,7 @@ using jfsx_rsa::kLimbs;
 using jfsx_rsa::kModBytes;
 
 // threads per workgroup of rsa_half_k
-#ifndef JFSX_RSA_LANES
-#define JFSX_RSA_LANES 64
-#endif
-constexpr int kRsaLanes = JFSX_RSA_LANES;
+constexpr int kRsaLanes = 64;
 
 __global__ __launch_bounds__(kRsaLanes) void rsa_half_k(const jfsx_rsa::Key *__restrict__ key, int n,
                                                         const uint8_t *__restrict__ ct, uint32_t *__restrict__ mh) {

@@ -28,7 +28,7 @@
 //     step with a ballot for the first difference.
 //   * the input bytes a step, a match's catch-up and length, its literal copy
 //     and its hash inserts need come from 256-byte register windows where
-//     they fall inside one (parse_fast_wave_w, JFSX_ZC_WIN bits), so most
+//     they fall inside one (parse_fast_wave_w), so most
 //     sequences cost two or three memory round trips, not eight.
 // The entropy stage of a block (literal Huffman coding, sequence FSE coding)
 // builds its tables on one lane (the library's serial code, jfsx_zstdc.h) and
@@ -40,23 +40,8 @@
 #include "jfsx_dev.h"
 #include "jfsx_zstdc.h"
 
-// 0: parse_fast_wave (every read from memory); else parse_fast_wave_w with
-// the window features named below (287: windows for everything + candidate
-// extensions; A/B in profiles/r4/ab_zstdc_win.txt)
-#ifndef JFSX_ZC_WIN
-#define JFSX_ZC_WIN 287
-#endif
 // lanes of the first search step after a match (doubling on each miss)
-#ifndef JFSX_ZC_K0
-#define JFSX_ZC_K0 2
-#endif
-// the entropy stage's byte loops and the block copies with several loads in
-// flight per lane (bits: 1 block copies, 2 histograms, 4 Huffman emission,
-// 8 FSE state chains, 16 sequence emission and codes; 0: one load per loop
-// iteration, the round-3 code; A/B in profiles/r4/ab_zstdc_win.txt)
-#ifndef JFSX_ZC_MLP
-#define JFSX_ZC_MLP 31
-#endif
+constexpr uint32_t kZcK0 = 2;
 
 namespace jfsx {
 
@@ -180,7 +165,7 @@ __device__ __forceinline__ void store_seq_wave(WSeq &ss, const uint8_t *lits, ui
 }
 
 // ---------------------------------------------------------------------------
-// Register windows (JFSX_ZC_WIN): 256 input bytes in the wave's VGPRs, lane L
+// Register windows: 256 input bytes in the wave's VGPRs, lane L
 // holding the image dword at w0 + 4L (zero past the object's end).  A read
 // inside a window is a ds_bpermute (per-lane position) or v_readlane (uniform
 // position), not a memory round trip; the search steps, the literal copies and
@@ -307,201 +292,17 @@ __device__ uint32_t count_back(ZWin &C, const ZImg &I, const uint8_t *src, int32
     return uni(mc >= avail ? avail : mc + count_wave(src + aa + mc, src + mX + 4 + mc, src + limit, lane));
 }
 
-// jzc::parse_fast on the wave: same sequences, same table, same repcodes.
-__device__ uint32_t parse_fast_wave(const uint8_t *src, int32_t istart, int32_t iend, uint32_t *htab, jzc::Params P,
-                                    uint32_t rep[2], WSeq &ss, uint32_t lane) {
-    const uint32_t hlog = P.hlog, mls = P.mls;
-    const int32_t endIndex = iend + 1;
-    const int32_t prefixStartIndex = jzc::prefix_start_index(endIndex, P.wlog);
-    const int32_t prefixStart = prefixStartIndex - 1;
-    const int32_t ilimit = iend - 8;
-    int32_t ip0 = istart, anchor = istart;
-    uint32_t offset_1 = rep[0], offset_2 = rep[1], offsetSaved = 0;
-    ip0 += (ip0 == prefixStart);
-    {
-        const int32_t cur = ip0 + 1;
-        const int32_t windowLow = jzc::prefix_start_index(cur, P.wlog);
-        const uint32_t maxRep = (uint32_t)(cur - windowLow);
-        if (offset_2 > maxRep) offsetSaved = offset_2, offset_2 = 0;
-        if (offset_1 > maxRep) offsetSaved = offset_1, offset_1 = 0;
-    }
-    const uint8_t *const iendp = src + iend;
-    gu32c *const T = (gu32c *)htab;
-    // speculation width: a step evaluates the next K iterations of the serial
-    // loop (a prefix, so the semantics are unchanged).  Each iteration costs a
-    // random hash-table read and a random candidate read; on text the first
-    // success comes within a few iterations, so after every match a step starts
-    // with JFSX_ZC_K0 lanes and doubles K on each step without a success.
-    uint32_t K = JFSX_ZC_K0;
-    while (ip0 + 1 < ilimit) {
-        // ---- one search step: iterations j = 0..K-1 of the serial loop ----
-        const int32_t d0 = ip0 - anchor;
-        int32_t d;
-        if (d0 < 2) {
-            d = d0 + 2 * (int32_t)lane;  // every step is 2 while d < 128
-        } else {
-            int32_t x = d0;
-            d = d0;
-            for (uint32_t j = 0; j < K; j++) {
-                if (lane == j) d = x;
-                x += (x >> 7) + 2;
-            }
-        }
-        const int32_t p = anchor + d;
-        const uint64_t amask = K >= 64 ? ~0ull : ((1ull << K) - 1ull);
-        const bool valid = lane < K && p + 1 < ilimit;
-        const uint64_t vmask = ballot(valid);
-        const int32_t pc = valid ? p : ip0;
-        uint64_t w0, w1;
-        load9(src, pc, w0, w1);
-        const uint32_t A = hash_w(w0, hlog, mls), B = hash_w(w1, hlog, mls);
-        const int32_t tA0 = (int32_t)T[A], tB0 = (int32_t)T[B];
-        const uint32_t v0 = (uint32_t)w0, v1 = (uint32_t)w1, r2 = (uint32_t)(w0 >> 16);
-        const bool okr = valid && offset_1 > 0 && ld32u(src + pc + 2 - (int32_t)offset_1) == r2;
-        bool ok0 = valid && tA0 > prefixStartIndex && ld32u(src + tA0 - 1) == v0;
-        bool ok1 = valid && tB0 > prefixStartIndex && ld32u(src + tB0 - 1) == v1;
-        int32_t tA = tA0, tB = tB0;
-        uint64_t sm = ballot(okr || ok0 || ok1);
-        uint64_t commit;
-        bool wA, wB;
-        if (sm & 1ull) {
-            // the first iteration succeeds on its own: it alone ran
-            commit = 1ull;
-            wA = lane == 0 && A != B;
-            wB = lane == 0;
-        } else {
-            // lanes whose writes share this lane's buckets: bit i of eqXY is
-            // set when lane i's hash Y equals this lane's hash X
-            uint64_t eqAA = ~0ull, eqBA = ~0ull, eqAB = ~0ull, eqBB = ~0ull;
-            if (K <= 16) {
-                // a narrow step: compare with each active lane's hashes directly
-                eqAA = eqBA = eqAB = eqBB = 0ull;
-                for (uint32_t i = 0; i < K; i++) {
-                    const uint32_t Ai = readlane(A, (int)i), Bi = readlane(B, (int)i);
-                    const uint64_t bit = 1ull << i;
-                    eqAA |= A == Ai ? bit : 0ull;
-                    eqBA |= A == Bi ? bit : 0ull;
-                    eqAB |= B == Ai ? bit : 0ull;
-                    eqBB |= B == Bi ? bit : 0ull;
-                }
-            } else {
-                // hashLog x 2 ballots
-                for (uint32_t bit = 0; bit < hlog; bit++) {
-                    const bool a = (A >> bit) & 1u, b = (B >> bit) & 1u;
-                    const uint64_t bA = ballot(a), bB = ballot(b);
-                    eqAA &= a ? bA : ~bA;
-                    eqBA &= a ? bB : ~bB;
-                    eqAB &= b ? bA : ~bA;
-                    eqBB &= b ? bB : ~bB;
-                }
-            }
-            eqAA &= vmask;
-            eqBA &= vmask;
-            eqAB &= vmask;
-            eqBB &= vmask;
-            const uint64_t below = lanes_below(lane), above = lanes_above(lane);
-            // reads: the latest earlier write to the bucket (B after A within an iteration)
-            {
-                const uint64_t ea = eqAA & below, eb = eqBA & below;
-                const int ia = ea ? 63 - __builtin_clzll(ea) : -1, ib = eb ? 63 - __builtin_clzll(eb) : -1;
-                const int src_l = ib >= ia ? ib : ia;
-                const int32_t pv = __shfl(p, src_l < 0 ? (int)lane : src_l, 64);
-                if (src_l >= 0) tA = pv + (ib >= ia ? 2 : 1);
-            }
-            {
-                const uint64_t ea = eqAB & below, eb = eqBB & below;
-                const int ia = ea ? 63 - __builtin_clzll(ea) : -1, ib = eb ? 63 - __builtin_clzll(eb) : -1;
-                const int src_l = ib >= ia ? ib : ia;
-                const int32_t pv = __shfl(p, src_l < 0 ? (int)lane : src_l, 64);
-                if (src_l >= 0) tB = pv + (ib >= ia ? 2 : 1);
-            }
-            if (tA != tA0) ok0 = valid && tA > prefixStartIndex && ld32u(src + tA - 1) == v0;
-            if (tB != tB0) ok1 = valid && tB > prefixStartIndex && ld32u(src + tB - 1) == v1;
-            sm = ballot(okr || ok0 || ok1);
-            commit = sm ? ((sm & (0ull - sm)) << 1) - 1ull : vmask;  // iterations that ran
-            const bool in = (commit >> lane) & 1ull;
-            wA = in && A != B && !((eqAA | eqBA) & above & commit);
-            wB = in && !((eqAB | eqBB) & above & commit);
-        }
-        if (wA) T[A] = (uint32_t)(p + 1);
-        if (wB) T[B] = (uint32_t)(p + 2);
-        if (!sm) {
-            if (vmask != amask) break;  // the serial loop ends inside this step
-            ip0 = anchor + unis(readlanes(d + (d >> 7) + 2, (int)K - 1));
-            K = K < 32 ? 2 * K : 64;  // any K0: never past 64
-            continue;
-        }
-        K = JFSX_ZC_K0;
-        // ---- the match of the first successful iteration f ----
-        const int f = __builtin_ctzll(sm);
-        const int32_t pf = unis(readlanes(p, f));
-        const bool fr = (readlane((uint32_t)okr, f) & 1u) != 0, f0 = (readlane((uint32_t)ok0, f) & 1u) != 0;
-        const int32_t current0 = pf + 1;
-        int32_t match0;
-        uint32_t mLength, offcode;
-        if (fr) {
-            const int32_t ip2 = pf + 2, repMatch = ip2 - (int32_t)offset_1;
-            mLength = ld8(src + ip2 - 1) == ld8(src + repMatch - 1) ? 1u : 0u;
-            ip0 = ip2 - (int32_t)mLength;
-            match0 = repMatch - (int32_t)mLength;
-            mLength += 4;
-            offcode = 0;
-        } else {
-            if (f0) {
-                ip0 = pf;
-                match0 = unis(readlanes(tA, f)) - 1;
-            } else {
-                ip0 = pf + 1;
-                match0 = unis(readlanes(tB, f)) - 1;
-            }
-            offset_2 = offset_1;
-            offset_1 = (uint32_t)(ip0 - match0);
-            offcode = offset_1 + 2;
-            mLength = 4;
-            const uint32_t lim = (uint32_t)min(ip0 - anchor, match0 - prefixStart);
-            const uint32_t back = lim ? back_wave(src + ip0, src + match0, lim, lane) : 0u;
-            ip0 -= (int32_t)back;
-            match0 -= (int32_t)back;
-            mLength += back;
-        }
-        mLength += count_wave(src + ip0 + mLength, src + match0 + mLength, iendp, lane);
-        mLength = uni(mLength);
-        store_seq_wave(ss, src + anchor, (uint32_t)(ip0 - anchor), offcode, mLength - 3, lane);
-        ip0 += (int32_t)mLength;
-        anchor = ip0;
-        if (ip0 <= ilimit) {
-            if (lane == 0) {
-                T[hash_w(ld64u(src + current0 + 1), hlog, mls)] = (uint32_t)(current0 + 2);
-                T[hash_w(ld64u(src + ip0 - 2), hlog, mls)] = (uint32_t)(ip0 - 1);
-            }
-            while (ip0 <= ilimit && offset_2 > 0 && uni(ld32u(src + ip0)) == uni(ld32u(src + ip0 - (int32_t)offset_2))) {
-                const uint32_t rLength = uni(count_wave(src + ip0 + 4, src + ip0 + 4 - offset_2, iendp, lane)) + 4;
-                const uint32_t t = offset_2;
-                offset_2 = offset_1;
-                offset_1 = t;
-                if (lane == 0) T[hash_w(ld64u(src + ip0), hlog, mls)] = (uint32_t)(ip0 + 1);
-                ip0 += (int32_t)rLength;
-                store_seq_wave(ss, src + anchor, 0, 0, rLength - 3, lane);
-                anchor = ip0;
-            }
-        }
-    }
-    rep[0] = offset_1 ? offset_1 : offsetSaved;
-    rep[1] = offset_2 ? offset_2 : offsetSaved;
-    return (uint32_t)(iend - anchor);
-}
-
-// parse_fast_wave with the input reads served from register windows where
-// they fall inside one (JFSX_ZC_WIN): the same sequences, table and repcodes.
-// W covers the search step's positions; C, loaded by count_back at the
+// jzc::parse_fast on the wave: same sequences, same table, same repcodes,
+// with the input reads served from register windows where they fall inside
+// one.  W covers the search step's positions; C, loaded by count_back at the
 // match, covers the match's end, the next anchor and often the next step.
-// ZWF (JFSX_ZC_WIN bits): 1 search positions, 2 count_back, 4 literal copies,
-// 8 hash inserts and repcode loop, 16 the match window as the next search window,
-// 256 candidate extensions (ZExt): a short match needs no count_back.  (Bits
-// 32, 64 and 128 -- everything after a match from one round of loads, the
-// next step's table reads in that round, repcode windows -- were measured
-// slower or equal and removed: profiles/r4/ab_zstdc_win.txt.)
-constexpr int ZWF = JFSX_ZC_WIN == 1 ? 31 : JFSX_ZC_WIN;
+// From windows: the search positions, count_back, the literal copies, the
+// hash inserts and the repcode loop; the match window becomes the next search
+// window; candidate extensions (ZExt) spare a short match its count_back.
+// (Everything after a match from one round of loads, the next step's table
+// reads in that round and repcode windows were measured slower or equal and
+// removed; the windowless parser and each feature alone are in
+// profiles/r4/ab_zstdc_win.txt.)
 __device__ uint32_t parse_fast_wave_w(const uint8_t *src, const ZImg I, int32_t istart, int32_t iend, uint32_t *htab,
                                       jzc::Params P, uint32_t rep[2], WSeq &ss, uint32_t lane) {
     const uint32_t hlog = P.hlog, mls = P.mls;
@@ -525,8 +326,8 @@ __device__ uint32_t parse_fast_wave_w(const uint8_t *src, const ZImg I, int32_t 
     // loop (a prefix, so the semantics are unchanged).  Each iteration costs a
     // random hash-table read and a random candidate read; on text the first
     // success comes within a few iterations, so after every match a step starts
-    // with JFSX_ZC_K0 lanes and doubles K on each step without a success.
-    uint32_t K = JFSX_ZC_K0;
+    // with kZcK0 lanes and doubles K on each step without a success.
+    uint32_t K = kZcK0;
     ZWin W, C;
     W.w0 = C.w0 = 0xfffff000u;  // empty
     W.w = C.w = 0;
@@ -553,8 +354,8 @@ __device__ uint32_t parse_fast_wave_w(const uint8_t *src, const ZImg I, int32_t 
         // hash insert at pf + 2) from W, reloaded at ip0 when it does not cover them
         const int32_t phi = unis(readlanes(p, (int)K - 1));
         const uint32_t span = (uint32_t)(phi - ip0) + 16u;
-        bool win = (ZWF & 1) && zw_has(W, I, ip0, span);
-        if ((ZWF & 1) && !win && span <= 240u) {
+        bool win = zw_has(W, I, ip0, span);
+        if (!win && span <= 240u) {
             zw_load(W, I, (uint32_t)ip0, lane);
             win = true;
         }
@@ -580,18 +381,13 @@ __device__ uint32_t parse_fast_wave_w(const uint8_t *src, const ZImg I, int32_t 
             okr = rq && ld32u(src + q) == r2;
         ZExt XA, XB;
         bool ok0, ok1;
-        if (ZWF & 256) {
-            zx_load(XA, I, tA0 - 1);
-            zx_load(XB, I, tB0 - 1);
-            const uint32_t sA = (uint32_t)(tA0 - 1 + (int32_t)I.sh) & 3u, sB = (uint32_t)(tB0 - 1 + (int32_t)I.sh) & 3u;
-            ok0 = valid && tA0 > prefixStartIndex &&
-                  (XA.in ? __builtin_amdgcn_alignbyte(XA.e[2], XA.e[1], sA) : ld32u(src + tA0 - 1)) == v0;
-            ok1 = valid && tB0 > prefixStartIndex &&
-                  (XB.in ? __builtin_amdgcn_alignbyte(XB.e[2], XB.e[1], sB) : ld32u(src + tB0 - 1)) == v1;
-        } else {
-            ok0 = valid && tA0 > prefixStartIndex && ld32u(src + tA0 - 1) == v0;
-            ok1 = valid && tB0 > prefixStartIndex && ld32u(src + tB0 - 1) == v1;
-        }
+        zx_load(XA, I, tA0 - 1);
+        zx_load(XB, I, tB0 - 1);
+        const uint32_t sA = (uint32_t)(tA0 - 1 + (int32_t)I.sh) & 3u, sB = (uint32_t)(tB0 - 1 + (int32_t)I.sh) & 3u;
+        ok0 = valid && tA0 > prefixStartIndex &&
+              (XA.in ? __builtin_amdgcn_alignbyte(XA.e[2], XA.e[1], sA) : ld32u(src + tA0 - 1)) == v0;
+        ok1 = valid && tB0 > prefixStartIndex &&
+              (XB.in ? __builtin_amdgcn_alignbyte(XB.e[2], XB.e[1], sB) : ld32u(src + tB0 - 1)) == v1;
         int32_t tA = tA0, tB = tB0;
         uint64_t sm = ballot(okr || ok0 || ok1);
         uint64_t commit;
@@ -663,7 +459,7 @@ __device__ uint32_t parse_fast_wave_w(const uint8_t *src, const ZImg I, int32_t 
             K = K < 32 ? 2 * K : 64;  // any K0: never past 64
             continue;
         }
-        K = JFSX_ZC_K0;
+        K = kZcK0;
         // ---- the match of the first successful iteration f ----
         const int f = __builtin_ctzll(sm);
         const int32_t pf = unis(readlanes(p, f));
@@ -675,14 +471,7 @@ __device__ uint32_t parse_fast_wave_w(const uint8_t *src, const ZImg I, int32_t 
         if (fr) {
             // the repcode match extends one byte back when ip2[-1] == repMatch[-1]
             const int32_t ip2 = pf + 2, repMatch = ip2 - (int32_t)offset_1;
-            uint32_t mc;
-            if (ZWF & 2) {
-                mc = count_back(C, I, src, ip2, repMatch, iend, 1u, back, lane);
-            } else {
-                back = ld8(src + ip2 - 1) == ld8(src + repMatch - 1) ? 1u : 0u;
-                mc = uni(count_wave(src + ip2 + 4, src + repMatch + 4, src + iend, lane));
-                C.w0 = 0xfffff000u;
-            }
+            const uint32_t mc = count_back(C, I, src, ip2, repMatch, iend, 1u, back, lane);
             ip0 = ip2 - (int32_t)back;
             match0 = repMatch - (int32_t)back;
             mLength = 4 + back + mc;
@@ -702,67 +491,60 @@ __device__ uint32_t parse_fast_wave_w(const uint8_t *src, const ZImg I, int32_t 
             const uint32_t lim = (uint32_t)min(ipX - anchor, match0 - prefixStart);
             uint32_t mc = 0;
             bool fast = false;
-            if (ZWF & 256) {
-                // a short match from the winner's extension and W: catch-up
-                // (<= 4 bytes) and ZSTD_count's first 12 bytes
-                const int32_t t0 = unis(readlanes(f0 ? tA0 : tB0, f));
-                const bool inf = (readlane((uint32_t)(f0 ? XA.in : XB.in), f) & 1u) != 0;
-                if (t0 - 1 == match0 && inf) {
-                    uint32_t u[6];
+            // a short match from the winner's extension and W: catch-up
+            // (<= 4 bytes) and ZSTD_count's first 12 bytes
+            const int32_t t0 = unis(readlanes(f0 ? tA0 : tB0, f));
+            const bool inf = (readlane((uint32_t)(f0 ? XA.in : XB.in), f) & 1u) != 0;
+            if (t0 - 1 == match0 && inf) {
+                uint32_t u[6];
 #pragma unroll
-                    for (int k = 0; k < 6; k++) u[k] = uni(readlane(f0 ? XA.e[k] : XB.e[k], f));
-                    const uint32_t s = (uint32_t)(match0 + (int32_t)I.sh) & 3u;
-                    const uint32_t L = (uint32_t)(iend - (ipX + 4));
-                    bool okf = false, okb = false;
-                    uint32_t mcf = 0, bk = 0;
-                    if (zw_has(W, I, ipX + 4, 20)) {
-                        const uint64_t c1 = zw_u64(W, I, ipX + 4);
-                        const uint32_t c2 = (uint32_t)zw_u64(W, I, ipX + 12);
-                        const uint64_t m1 = (uint64_t)__builtin_amdgcn_alignbyte(u[3], u[2], s) |
-                                            ((uint64_t)__builtin_amdgcn_alignbyte(u[4], u[3], s) << 32);
-                        const uint32_t m2 = __builtin_amdgcn_alignbyte(u[5], u[4], s);
-                        const uint64_t x1 = c1 ^ m1;
-                        const uint32_t x2 = c2 ^ m2;
-                        const uint32_t j = x1 ? (uint32_t)__builtin_ctzll(x1) >> 3
-                                              : x2 ? 8u + ((uint32_t)__builtin_ctz(x2) >> 3) : 12u;
-                        if (j < 12u || L <= 12u) {
-                            mcf = j < L ? j : L;
-                            okf = true;
-                        }
-                    }
-                    if (lim == 0) {
-                        okb = true;
-                    } else if (zw_has(W, I, ipX - 4, 12)) {
-                        const uint32_t y = (uint32_t)zw_u64(W, I, ipX - 4) ^ __builtin_amdgcn_alignbyte(u[1], u[0], s);
-                        const uint32_t eq = y ? (uint32_t)__builtin_clz(y) >> 3 : 4u;
-                        if (eq < 4u || lim <= 4u) {
-                            bk = eq < lim ? eq : lim;
-                            okb = true;
-                        }
-                    }
-                    if (okf && okb) {
-                        mc = mcf;
-                        back = bk;
-                        fast = true;
-                        C = W;
+                for (int k = 0; k < 6; k++) u[k] = uni(readlane(f0 ? XA.e[k] : XB.e[k], f));
+                const uint32_t s = (uint32_t)(match0 + (int32_t)I.sh) & 3u;
+                const uint32_t L = (uint32_t)(iend - (ipX + 4));
+                bool okf = false, okb = false;
+                uint32_t mcf = 0, bk = 0;
+                if (zw_has(W, I, ipX + 4, 20)) {
+                    const uint64_t c1 = zw_u64(W, I, ipX + 4);
+                    const uint32_t c2 = (uint32_t)zw_u64(W, I, ipX + 12);
+                    const uint64_t m1 = (uint64_t)__builtin_amdgcn_alignbyte(u[3], u[2], s) |
+                                        ((uint64_t)__builtin_amdgcn_alignbyte(u[4], u[3], s) << 32);
+                    const uint32_t m2 = __builtin_amdgcn_alignbyte(u[5], u[4], s);
+                    const uint64_t x1 = c1 ^ m1;
+                    const uint32_t x2 = c2 ^ m2;
+                    const uint32_t j = x1 ? (uint32_t)__builtin_ctzll(x1) >> 3
+                                          : x2 ? 8u + ((uint32_t)__builtin_ctz(x2) >> 3) : 12u;
+                    if (j < 12u || L <= 12u) {
+                        mcf = j < L ? j : L;
+                        okf = true;
                     }
                 }
+                if (lim == 0) {
+                    okb = true;
+                } else if (zw_has(W, I, ipX - 4, 12)) {
+                    const uint32_t y = (uint32_t)zw_u64(W, I, ipX - 4) ^ __builtin_amdgcn_alignbyte(u[1], u[0], s);
+                    const uint32_t eq = y ? (uint32_t)__builtin_clz(y) >> 3 : 4u;
+                    if (eq < 4u || lim <= 4u) {
+                        bk = eq < lim ? eq : lim;
+                        okb = true;
+                    }
+                }
+                if (okf && okb) {
+                    mc = mcf;
+                    back = bk;
+                    fast = true;
+                    C = W;
+                }
             }
-            if (fast) {
-            } else if (ZWF & 2) {
+            if (!fast) {
                 mc = count_back(C, I, src, ipX, match0, iend, lim < 64u ? lim : 64u, back, lane);
                 if (back == 64u && lim > 64u) back = 64u + back_wave(src + ipX - 64, src + match0 - 64, lim - 64u, lane);
-            } else {
-                back = lim ? back_wave(src + ipX, src + match0, lim, lane) : 0u;
-                mc = uni(count_wave(src + ipX + 4, src + match0 + 4, src + iend, lane));
-                C.w0 = 0xfffff000u;
             }
             ip0 = ipX - (int32_t)back;
             match0 -= (int32_t)back;
             mLength = 4 + back + mc;
         }
         mLength = uni(mLength);
-        if ((ZWF & 4) && zw_has(W, I, anchor, (uint32_t)(ip0 - anchor)))
+        if (zw_has(W, I, anchor, (uint32_t)(ip0 - anchor)))
             store_seq_win(ss, W, I, anchor, (uint32_t)(ip0 - anchor), offcode, mLength - 3, lane);
         else
             store_seq_wave(ss, src + anchor, (uint32_t)(ip0 - anchor), offcode, mLength - 3, lane);
@@ -770,9 +552,9 @@ __device__ uint32_t parse_fast_wave_w(const uint8_t *src, const ZImg I, int32_t 
         anchor = ip0;
         if (ip0 <= ilimit) {
             {
-                const uint64_t h1 = (ZWF & 8) && zw_has(W, I, current0 + 1, 12) ? zw_u64(W, I, current0 + 1)
+                const uint64_t h1 = zw_has(W, I, current0 + 1, 12) ? zw_u64(W, I, current0 + 1)
                                                                               : ld64u(src + current0 + 1);
-                const uint64_t h2 = (ZWF & 8) && zw_has(C, I, ip0 - 2, 12) ? zw_u64(C, I, ip0 - 2) : ld64u(src + ip0 - 2);
+                const uint64_t h2 = zw_has(C, I, ip0 - 2, 12) ? zw_u64(C, I, ip0 - 2) : ld64u(src + ip0 - 2);
                 if (lane == 0) {
                     T[hash_w(h1, hlog, mls)] = (uint32_t)(current0 + 2);
                     T[hash_w(h2, hlog, mls)] = (uint32_t)(ip0 - 1);
@@ -780,15 +562,14 @@ __device__ uint32_t parse_fast_wave_w(const uint8_t *src, const ZImg I, int32_t 
             }
             for (;;) {
                 if (!(ip0 <= ilimit && offset_2 > 0)) break;
-                const uint32_t a = (ZWF & 8) && zw_has(C, I, ip0, 8) ? (uint32_t)zw_u64(C, I, ip0) : uni(ld32u(src + ip0));
+                const uint32_t a = zw_has(C, I, ip0, 8) ? (uint32_t)zw_u64(C, I, ip0) : uni(ld32u(src + ip0));
                 const int32_t rp = ip0 - (int32_t)offset_2;
-                const uint32_t bq = (ZWF & 8) && zw_has(C, I, rp, 12) ? (uint32_t)zw_u64(C, I, rp) : uni(ld32u(src + rp));
+                const uint32_t bq = zw_has(C, I, rp, 12) ? (uint32_t)zw_u64(C, I, rp) : uni(ld32u(src + rp));
                 if (a != bq) break;
-                const uint64_t h3 = (ZWF & 8) && zw_has(C, I, ip0, 12) ? zw_u64(C, I, ip0) : ld64u(src + ip0);
+                const uint64_t h3 = zw_has(C, I, ip0, 12) ? zw_u64(C, I, ip0) : ld64u(src + ip0);
                 uint32_t b0;
                 const uint32_t rLength =
-                    ((ZWF & 2) ? count_back(C, I, src, ip0, rp, iend, 0u, b0, lane)
-                               : uni(count_wave(src + ip0 + 4, src + rp + 4, src + iend, lane))) + 4;
+                    count_back(C, I, src, ip0, rp, iend, 0u, b0, lane) + 4;
                 const uint32_t t = offset_2;
                 offset_2 = offset_1;
                 offset_1 = t;
@@ -799,7 +580,7 @@ __device__ uint32_t parse_fast_wave_w(const uint8_t *src, const ZImg I, int32_t 
             }
         }
         // the next search starts at anchor: C often covers it already
-        if ((ZWF & 16) && zw_has(C, I, anchor, 2 * JFSX_ZC_K0 + 16)) W = C;
+        if (zw_has(C, I, anchor, 2 * kZcK0 + 16)) W = C;
     }
     rep[0] = offset_1 ? offset_1 : offsetSaved;
     rep[1] = offset_2 ? offset_2 : offsetSaved;
@@ -928,19 +709,10 @@ __device__ __noinline__ void copy_run(uint8_t *dst, const uint8_t *src, uint32_t
         }
     }
 }
-// the same, one byte per lane per iteration (the round-3 loop; A/B)
-__device__ __forceinline__ void copy_bytes(uint8_t *dst, const uint8_t *src, uint32_t n, uint32_t lane) {
-#if JFSX_ZC_MLP & 1
-    copy_run(dst, src, n, lane);
-#else
-    for (uint32_t o = lane; o < n; o += 64) *(gu8c *)(dst + o) = (uint8_t)ld8(src + o);
-#endif
-}
 
 // histogram of the bytes p[0, n) (p 4-byte aligned, readable up to the next
 // dword) into LDS counters by atomics
 __device__ __forceinline__ void hist_bytes(uint32_t *cnt, const uint8_t *p, uint32_t n, uint32_t lane) {
-#if JFSX_ZC_MLP & 2
 #pragma unroll 4
     for (uint32_t i = 4 * lane; i < n; i += 256) {
         const uint32_t w = ld32a(p + i);
@@ -948,23 +720,7 @@ __device__ __forceinline__ void hist_bytes(uint32_t *cnt, const uint8_t *p, uint
         for (uint32_t k = 0; k < 4; k++)
             if (i + k < n) atomicAdd(&cnt[(w >> (8 * k)) & 255u], 1u);
     }
-#else
-    for (uint32_t i = lane; i < n; i += 64) atomicAdd(&cnt[ld8(p + i)], 1u);
-#endif
 }
-// diagnostic build (-DJFSX_ZC_TRACE): lane 0 prints each stage of the entropy
-// stage as it is reached (device printf is a hostcall: lines appear while the
-// kernel runs, so a hang shows its last stage)
-#ifdef JFSX_ZC_TRACE
-#define ZT(...)                                    \
-    do {                                           \
-        if (threadIdx.x == 0) printf(__VA_ARGS__); \
-    } while (0)
-#else
-#define ZT(...) \
-    do {        \
-    } while (0)
-#endif
 
 // HUF_compress_internal without the encoding: 0 not compressible, 1 RLE,
 // 2 encode with the old table (W->next.ct), 3 encode with the new table
@@ -1036,7 +792,6 @@ __device__ uint32_t huf_streams_wave(uint8_t *body, uint32_t o, uint32_t cap, co
     wave_sync();
     // this lane's run, last symbol first, from bit `before` of its stream
     uint64_t q = 8ull * my0 + before;
-#if JFSX_ZC_MLP & 4
     if (c1 > c0) {
         // the run backwards in 16-byte groups, the next group loaded before
         // this one's ORs
@@ -1060,13 +815,6 @@ __device__ uint32_t huf_streams_wave(uint8_t *body, uint32_t o, uint32_t cap, co
             for (int k = 0; k < 4; k++) r[k] = rn[k];
         }
     }
-#else
-    for (int32_t i = (int32_t)c1 - 1; i >= (int32_t)c0; i--) {
-        const uint32_t b = ld8(lit + s0 + i);
-        or_bits((uint32_t *)body, q, ct.val[b], ct.nb[b]);
-        q += ct.nb[b];
-    }
-#endif
     if (j == 0) or_bits((uint32_t *)body, 8ull * my0 + total, 1, 1);  // end mark
     if (!single && lane == 0) {
         jzc::wr16(body + o, sz[0]);
@@ -1146,7 +894,7 @@ __device__ uint32_t literals_wave(jzc::Work &W, uint8_t *body, const uint8_t *li
             else if (fl == 2) jzc::wr16(body, jzc::kSetBasic + (1u << 2) + (n << 4));
             else jzc::wr24(body, jzc::kSetBasic + (3u << 2) + (n << 4));
         }
-        copy_bytes(body + fl, lit, n, lane);
+        copy_run(body + fl, lit, n, lane);
         wave_sync();
         return fl + n;
     }
@@ -1201,14 +949,12 @@ __device__ uint32_t sequences_wave(jzc::Work &W, uint8_t *body, uint32_t o, uint
                                    const uint8_t *llc, const uint8_t *mlc, const uint8_t *ofc, uint16_t *rec,
                                    uint32_t n, uint32_t lane) {
     __shared__ uint32_t fin[3];
-    ZT("zc: seq chains n %u\n", n);
     if (lane < 3) {
         const jzc::FseCT &ct = lane == 0 ? W.sw.of : lane == 1 ? W.sw.ml : W.sw.ll;
         const uint8_t *cd = lane == 0 ? ofc : lane == 1 ? mlc : llc;
         gu16c *r = (gu16c *)(rec + (size_t)lane * jzc::kMaxSeq);
         jzc::FseState st;
         jzc::fse_init_state2(st, ct, ld8(cd + n - 1));
-#if JFSX_ZC_MLP & 8
         // the codes in aligned 16-byte groups (cd is 16-byte aligned), the
         // next group's load in flight while this one's 16 steps run
         const int32_t top = (int32_t)n - 2;
@@ -1232,14 +978,6 @@ __device__ uint32_t sequences_wave(jzc::Work &W, uint8_t *body, uint32_t o, uint
                 v = vn;
             }
         }
-#else
-        for (int32_t i = (int32_t)n - 2; i >= 0; i--) {
-            const uint32_t c = ld8(cd + i);
-            const uint32_t nb = (st.value + ct.dnb[c]) >> 16;
-            r[i] = (uint16_t)((nb << 12) | (st.value & ((1u << nb) - 1)));
-            st.value = ct.state[(int32_t)(st.value >> nb) + ct.dfs[c]];
-        }
-#endif
         fin[lane] = st.value;
     }
     wave_sync();
@@ -1254,10 +992,8 @@ __device__ uint32_t sequences_wave(jzc::Work &W, uint8_t *body, uint32_t o, uint
         bits += jzc::kLLBits[l] + jzc::kMLBits[m] + f;
         if (i + 1 < n) bits += (rOF[i] >> 12) + (rML[i] >> 12) + (rLL[i] >> 12);
     }
-    ZT("zc: seq bits\n");
     const uint32_t before = suffix_excl(bits, lane, 64);
     const uint32_t total = __shfl(before + bits, 0, 64);
-    ZT("zc: seq total %u\n", total);
     const uint32_t tl = W.sw.ml.tableLog + W.sw.of.tableLog + W.sw.ll.tableLog;
     const uint32_t bytes = (total + tl + 1 + 7) >> 3;
     if (o + bytes + 16 > cap) return 0;
@@ -1265,7 +1001,6 @@ __device__ uint32_t sequences_wave(jzc::Work &W, uint8_t *body, uint32_t o, uint
     wave_sync();
     uint64_t q = 8ull * o + before;
     uint32_t *base = (uint32_t *)body;
-#if JFSX_ZC_MLP & 16
     constexpr int kG = 4;  // sequences whose inputs are loaded before their ORs
     for (int32_t i0 = (int32_t)c1 - 1; i0 >= (int32_t)c0; i0 -= kG) {
         uint32_t L[kG], M[kG], F[kG], RA[kG], RB[kG], RC[kG];
@@ -1299,27 +1034,6 @@ __device__ uint32_t sequences_wave(jzc::Work &W, uint8_t *body, uint32_t o, uint
             }
         }
     }
-#else
-    for (int32_t i = (int32_t)c1 - 1; i >= (int32_t)c0; i--) {
-        const uint32_t l = ld8(llc + i), m = ld8(mlc + i), f = ld8(ofc + i);
-        const jzc::SeqDef d = seq[i];
-        if ((uint32_t)i + 1 < n) {
-            const uint32_t a = rOF[i], b = rML[i], c = rLL[i];
-            or_bits(base, q, a & 0xfff, a >> 12);
-            q += a >> 12;
-            or_bits(base, q, b & 0xfff, b >> 12);
-            q += b >> 12;
-            or_bits(base, q, c & 0xfff, c >> 12);
-            q += c >> 12;
-        }
-        or_bits(base, q, d.ll, jzc::kLLBits[l]);
-        q += jzc::kLLBits[l];
-        or_bits(base, q, d.ml, jzc::kMLBits[m]);
-        q += jzc::kMLBits[m];
-        or_bits(base, q, d.offset, f);
-        q += f;
-    }
-#endif
     if (lane == 0) {
         uint64_t e = 8ull * o + total;
         or_bits(base, e, fin[1], W.sw.ml.tableLog);
@@ -1339,9 +1053,7 @@ __device__ uint32_t sequences_wave(jzc::Work &W, uint8_t *body, uint32_t o, uint
 __device__ uint64_t block_body_wave(jzc::Work &W, const WSeq &ss, uint8_t *codes, uint16_t *rec, uint8_t *body,
                                     uint32_t bs, uint32_t lane) {
     __shared__ uint32_t bc[2];
-    ZT("zc: block body nlit %u nseq %u bs %u\n", ss.nlit, ss.nseq, bs);
     uint32_t op = literals_wave(W, body, ss.lit, ss.nlit, lane);
-    ZT("zc: literals -> %u\n", op);
     const uint32_t nbSeq = ss.nseq;
     if (lane == 0) {
         if (nbSeq < 128) {
@@ -1357,7 +1069,6 @@ __device__ uint64_t block_body_wave(jzc::Work &W, const WSeq &ss, uint8_t *codes
     op += nbSeq < 128 ? 1 : nbSeq < jzc::kLongNbSeq ? 2 : 3;
     if (nbSeq != 0) {
         uint8_t *llc = codes, *mlc = codes + jzc::kMaxSeq, *ofc = codes + 2 * jzc::kMaxSeq;
-#if JFSX_ZC_MLP & 16
         for (uint32_t i0 = lane; i0 < nbSeq; i0 += 256) {
             jzc::SeqDef D[4];
 #pragma unroll
@@ -1373,14 +1084,6 @@ __device__ uint64_t block_body_wave(jzc::Work &W, const WSeq &ss, uint8_t *codes
                 }
             }
         }
-#else
-        for (uint32_t i = lane; i < nbSeq; i += 64) {
-            const jzc::SeqDef d = ss.seq[i];
-            *(gu8c *)(llc + i) = (uint8_t)jzc::ll_code(d.ll);
-            *(gu8c *)(ofc + i) = (uint8_t)jzc::highbit32(d.offset);
-            *(gu8c *)(mlc + i) = (uint8_t)jzc::ml_code(d.ml);
-        }
-#endif
         wave_sync();
         if (lane == 0) {
             if (ss.long_id == 1) llc[ss.long_pos] = jzc::kMaxLL;
@@ -1395,22 +1098,18 @@ __device__ uint64_t block_body_wave(jzc::Work &W, const WSeq &ss, uint8_t *codes
         for (uint32_t k = 0; k < 3; k++) {
             uint32_t max, mf;
             hist_codes_wave(W, cds[k], nbSeq, maxIn[k], lane, max, mf);
-            ZT("zc: hist %u max %u mf %u\n", k, max, mf);
             const uint32_t type = k == 1 ? jzc::select_type(mf, nbSeq, 5, max <= jzc::kDefaultMaxOff)
                                          : jzc::select_type(mf, nbSeq, 6, true);
             if (lane == 0) bc[0] = build_table_lane(&W, body + op, k, type, max, cds[k], nbSeq);
             wave_sync();
             const uint32_t t = uni(bc[0]);
-            ZT("zc: table %u type %u size %u\n", k, type, t);
             if (type == jzc::kSetCompressed) lastNCount = (int32_t)op;
             op += t;
             types[k] = type;
         }
         if (lane == 0) body[seqHead] = (uint8_t)((types[0] << 6) + (types[1] << 4) + (types[2] << 2));
         if (op + 16 >= jzc::kBodyCap) return 0;
-        ZT("zc: sequences at %u\n", op);
         const uint32_t b = sequences_wave(W, body, op, jzc::kBodyCap, ss.seq, llc, mlc, ofc, rec, nbSeq, lane);
-        ZT("zc: sequences -> %u\n", b);
         if (b == 0) return 0;
         op += b;
         if (lastNCount >= 0 && (int32_t)op - lastNCount < 4) return 0;
@@ -1430,13 +1129,10 @@ __device__ uint64_t compress_object(const uint8_t *src, uint64_t n, uint8_t *dst
                                     jzc::SeqDef *seqs, uint8_t *lits, uint8_t *codes, uint8_t *body, uint16_t *rec,
                                     jzc::Work &W, uint32_t lane) {
     const jzc::Params P = jzc::level1_params(n);
-    ZT("zc: params %u %u %u\n", P.wlog, P.hlog, P.mls);
     __shared__ uint32_t bcast;
     if (lane == 0) bcast = frame_header_lane(dst, n, P);
-    ZT("zc: header %u\n", bcast);
     __syncthreads();
     uint64_t op = uni(bcast);
-    ZT("zc: op %lu\n", (unsigned long)op);
     if (n == 0) {
         if (lane == 0) jzc::wr24(dst + op, 1);
         return op + 3;
@@ -1457,23 +1153,17 @@ __device__ uint64_t compress_object(const uint8_t *src, uint64_t n, uint8_t *dst
             WSeq ss{seqs, lits, 0, 0, 0, 0};
             uint32_t nrep[2] = {rep[0], rep[1]};
             __syncthreads();  // the table clear / last block's work has landed
-            ZT("zc: parse block at %lu bs %u\n", (unsigned long)pos, bs);
 #ifdef JFSX_ZC_STAMP
             const uint64_t t_p0 = wall_clock64();
 #endif
-#if JFSX_ZC_WIN
             const ZImg I{(const uint8_t *)((uintptr_t)src & ~(uintptr_t)3), (uint32_t)((uintptr_t)src & 3), (uint32_t)n};
             const uint32_t lastLL =
                 parse_fast_wave_w(src, I, (int32_t)pos, (int32_t)(pos + bs), htab, P, nrep, ss, lane);
-#else
-            const uint32_t lastLL = parse_fast_wave(src, (int32_t)pos, (int32_t)(pos + bs), htab, P, nrep, ss, lane);
-#endif
 #ifdef JFSX_ZC_STAMP
             const uint64_t t_p1 = wall_clock64();
             if (lane == 0) g_zc_parse += t_p1 - t_p0, g_zc_nseq += ss.nseq;
 #endif
-            ZT("zc: parsed nseq %u lastLL %u\n", ss.nseq, lastLL);
-            copy_bytes(lits + ss.nlit, src + pos + bs - lastLL, lastLL, lane);
+            copy_run(lits + ss.nlit, src + pos + bs - lastLL, lastLL, lane);
             ss.nlit += lastLL;
             __syncthreads();  // sequences and literals visible to every lane
 #ifdef JFSX_ZC_LANE0_ENTROPY
@@ -1505,7 +1195,7 @@ __device__ uint64_t compress_object(const uint8_t *src, uint64_t n, uint8_t *dst
         }
         if (cSize == 0) {
             if (lane == 0) jzc::wr24(dst + op, last + (bs << 3));
-            copy_bytes(dst + op + 3, ip, bs, lane);
+            copy_run(dst + op + 3, ip, bs, lane);
             op += 3 + bs;
         } else if (cSize == 1) {
             if (lane == 0) {
@@ -1515,7 +1205,7 @@ __device__ uint64_t compress_object(const uint8_t *src, uint64_t n, uint8_t *dst
             op += 4;
         } else {
             if (lane == 0) jzc::wr24(dst + op, last + (2u << 1) + ((uint32_t)cSize << 3));
-            copy_bytes(dst + op + 3, body, (uint32_t)cSize, lane);
+            copy_run(dst + op + 3, body, (uint32_t)cSize, lane);
             op += 3 + cSize;
         }
         pos += bs;
@@ -1538,10 +1228,8 @@ __device__ uint64_t compress_object(const uint8_t *src, uint64_t n, uint8_t *dst
 // waves finishes in about n / W object times instead of ceil(n / W).
 // 4 waves per SIMD (<= 128 VGPRs): with the 9.3 KiB Work, 16 objects per CU
 // are in flight, which is what a latency-bound parser needs
-#ifndef JFSX_ZC_WPE
-#define JFSX_ZC_WPE 4
-#endif
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(JFSX_ZC_WPE))) void zstd_compress_k(const ZDev *__restrict__ blks, ZOut *__restrict__ outs,
+constexpr int kZcWpe = 4;  // waves per SIMD the compiler plans for
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kZcWpe))) void zstd_compress_k(const ZDev *__restrict__ blks, ZOut *__restrict__ outs,
                                                       uint8_t *__restrict__ scratch, int n,
                                                       uint32_t *__restrict__ queue) {
     __shared__ jzc::Work W;
@@ -1555,7 +1243,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(JFSX_ZC_WPE)
     uint16_t *const rec = (uint16_t *)(body + kZcBody);
     for (int obj = (int)blockIdx.x; obj < n;) {
         const ZDev b = blks[obj];
-        ZT("zc: object %d len %lu\n", obj, (unsigned long)b.len);
 #ifdef JFSX_ZC_SCALAR
         uint64_t r = 0;
         if (lane == 0) r = jzc::compress_frame(b.src, b.len, b.dst, htab, seqs, lits, codes, body, W);
@@ -1572,7 +1259,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(JFSX_ZC_WPE)
                    (unsigned long)g_zc_parse, (unsigned long)g_zc_entropy, (unsigned long)g_zc_nseq);
 #endif
 #endif
-        ZT("zc: object %d -> %lu\n", obj, (unsigned long)r);
         if (lane == 0) {
             outs[obj].out_len = r;
             outs[obj].status = JFSX_OK;

@@ -1,4 +1,4 @@
-# CPU emulation of the JFSX_CRC_BYTE lane algorithm of jfsx_crc.hip (table layout, v_perm selectors,
+# CPU emulation of the byte-table lane algorithm of jfsx_crc.hip (table layout, v_perm selectors,
 # slice-by-4 chains, 4096-B span shift, lane-to-segment-end shift) against bytewise CRC32C.
 # Standalone check: python3 tools/emu_crc_byte.py
 import numpy as np, os
