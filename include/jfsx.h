@@ -21,6 +21,9 @@
  *   (+ JFSX_CRC_CT)      stored object, fused with Seal/Open        (s3.go:140-146,173-176)
  *   jfsx_load_batch      cachedStore.load's Decrypt + Decompress +  pkg/chunk/cached_store.go:673-748
  *                        bcache.cache's checksum(), one call        (disk_cache.go:433-483)
+ *   jfsx_store_batch     uploadStagingFile's verified re-read +     pkg/chunk/cached_store.go:944-999, :371-413
+ *                        upload's Compress + Encrypt + checksums,   (disk_cache.go:433-483, checksum.go:31-53)
+ *                        one call
  *   JFSX_AES256GCM /     NewDataEncryptor algo "aes256gcm-rsa" /    pkg/object/encrypt.go:142-162
  *   JFSX_CHACHA20P1305   "chacha20-rsa"
  *
@@ -569,6 +572,65 @@ typedef struct jfsx_lblk {
     int32_t codec_info;   /* out: zstd, why the serial decoder took it (as jfsx_zblk.reserved) */
 } jfsx_lblk;
 int jfsx_load_batch(jfsx_ctx *ctx, int algo, int codec, int n, jfsx_lblk *blks, int crc_mode, int mem);
+
+/* One-call block store: the write side of a volume formatted with --compress
+ * lz4 / zstd -- the staged re-read of --writeback (uploadStagingFile ->
+ * cacheFile.ReadAt's CRC verify, pkg/chunk/cached_store.go:944-999) or
+ * bcache.stage's checksum() of the page (:439; disk_cache.go:433-483),
+ * cachedStore.upload's Compress (:371-413), store.put's Encrypt
+ * (encrypt.go:164-194) and the object store's checksum of what is put
+ * (pkg/object/checksum.go:31-53) -- for a batch of pages in one synchronous
+ * call.  JFSX_MEM_HOST moves each page up once and each stored image down
+ * once; the compressed bytes never leave device memory.  The call waits twice:
+ * the Seal is planned from the compressed lengths, which come back first (a
+ * few dozen bytes per block).
+ *   algo      JFSX_AES256GCM, JFSX_CHACHA20P1305, or JFSX_CIPHER_NONE (dst
+ *             receives the compressed block itself)
+ *   codec     JFSX_CODEC_LZ4 or JFSX_CODEC_ZSTD (a volume with no codec is
+ *             served by jfsx_seal_batch already: JFSX_CRC_BOTH gives both
+ *             checksums)
+ *   crc_mode  the low two bits are about the page: JFSX_CRC_NONE, JFSX_CRC_GEN
+ *             (checksum(page) into crc, the direct upload of wSlice.upload) or
+ *             JFSX_CRC_VERIFY (crc holds the staged file's CRCs).  JFSX_CRC_CT
+ *             may be OR'ed in, or given alone: obj_crc receives the object
+ *             checksum CRC32C(hdr || dst[0, out_len) || tag), the value
+ *             jfsx_object_crc32c folds (without a cipher: CRC32C(hdr || image))
+ *   mem       JFSX_MEM_HOST: pageable or pinned memory at any alignment; only
+ *             dst[0, out_len) is written.  JFSX_MEM_DEVICE: src 16-byte aligned
+ *             when the page CRC runs (GEN / VERIFY), dst 16-byte aligned when a
+ *             cipher or JFSX_CRC_CT touches it, dst distinct from src, crc in
+ *             device memory (hdr stays host memory)
+ * Anything else is JFSX_EINVAL, and so are the limits of the separate calls
+ * (len <= 0x7E000000 and the ciphers' own), reserved != 0, and dst_cap below
+ * jfsx_lz4_bound(len) / jfsx_zstd_bound(len) -- all before anything runs.  The bytes are those of the separate calls: jfsx_lz4/zstd_compress_batch,
+ * then jfsx_seal_batch on its output with the same key and nonce; tag, crc and
+ * obj_crc likewise.  A block whose page fails JFSX_CRC_VERIFY gets JFSX_ECRC
+ * with crc_bad_seg / crc_got / crc_expect as jfsx_blk reports them, out_len 0,
+ * tag and obj_crc zero; neither the compressor nor the cipher is started on its
+ * bytes, dst[0, dst_cap) is not written, and the other blocks of the batch are
+ * unaffected.  jfsx_metrics counts what the separate calls would: crc_* over the
+ * n pages (crc_fail for JFSX_ECRC), lz4c_* / zstdc_* and seal_* over the blocks
+ * that passed the verify (seal_bytes = the sum of out_len), and the CRC launch
+ * that JFSX_CRC_CT adds without a cipher as jfsx_crc32c_segments would. */
+typedef struct jfsx_sblk {
+    uint8_t key[32];      /* as jfsx_blk; ignored with JFSX_CIPHER_NONE           */
+    uint8_t nonce[12];
+    uint32_t reserved;    /* must be 0                                            */
+    uint8_t tag[16];      /* out; zero with JFSX_CIPHER_NONE or a failed block    */
+    const void *src;      /* the page                                             */
+    uint64_t len;
+    void *dst;            /* stored image: C (no header, no tag), or the compressed block */
+    uint64_t dst_cap;     /* >= jfsx_lz4_bound(len) / jfsx_zstd_bound(len)        */
+    uint8_t *crc;         /* GEN: out, VERIFY: in; 4*max(1,ceil(len/32K)) B; unused otherwise */
+    const void *hdr;      /* JFSX_CRC_CT: object header bytes, HOST memory, nullable */
+    uint32_t hdr_len;
+    uint32_t obj_crc;     /* out with JFSX_CRC_CT: CRC32C(hdr || dst[0,out_len) || tag) */
+    uint64_t out_len;     /* out: bytes of the stored image, 0 for a failed block */
+    int32_t status;       /* out: JFSX_OK / JFSX_ECRC                             */
+    int32_t crc_bad_seg;  /* out, as jfsx_blk (VERIFY)                            */
+    uint32_t crc_got, crc_expect;
+} jfsx_sblk;
+int jfsx_store_batch(jfsx_ctx *ctx, int algo, int codec, int n, jfsx_sblk *blks, int crc_mode, int mem);
 
 /* header helper: returns wrapped-key length and offset/size of the nonce so a
  * caller can unwrap the key first (encrypt.go:197-205) */

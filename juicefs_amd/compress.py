@@ -19,7 +19,8 @@ jfsx_zstd_compress_batch (jfsx_zstdc.hip) writes the zstd library's level-1
 frames byte for byte, jfsx_zstd_decompress_batch (jfsx_zstd.hip) decodes as
 ZSTD_decompress.  load_blocks_fused is load_block as one engine call
 (jfsx_load_batch: Decrypt, Decompress and the cache's checksum() chained in
-device memory).
+device memory), upload_blocks_fused is upload_block the same way
+(jfsx_store_batch: checksum(), Compress, Encrypt and the object checksum).
 """
 from . import engine as E
 from .encrypt import default_engine
@@ -356,3 +357,49 @@ def load_blocks_fused(store, keys, lengths, compressor, enc=None, checksums=True
         pages.append(page)
         crcs.append(crc)
     return (pages, crcs) if checksums else pages
+
+
+def upload_blocks_fused(store, keys, blocks, compressor, enc=None, checksums=True):
+    """cachedStore.upload for a batch in one engine call (jfsx_store_batch): each
+    block is checksummed (bcache.stage's checksum(), disk_cache.go:433-483),
+    compressed and, with enc (a DataEncryptor), sealed without leaving the
+    device in between (cached_store.go:371-413, :439); the raw `store` receives
+    header || C || tag per block, or the compressed block itself without enc --
+    the objects load_blocks(NewEncrypted(store, enc) or store, ...) and
+    load_blocks_fused read back.
+
+    Key and nonce of block i are drawn from enc's rand in DataEncryptor.Encrypt's
+    order (key, then the wrap on the host by keyEncryptor.Encrypt, then the
+    nonce; encrypt.go:165-180), block by block.
+    Returns (objects, crcs) with crcs[i] == checksum(blocks[i]), or the objects
+    alone with checksums=False."""
+    if not isinstance(compressor, (LZ4, ZStandard)):
+        raise ValueError("upload_blocks_fused needs the lz4 or zstd compressor (an uncompressed volume uploads "
+                         "through DataEncryptor.EncryptBatch)")
+    eng = compressor.eng
+    codec = E.CODEC_LZ4 if isinstance(compressor, LZ4) else E.CODEC_ZSTD
+    blocks = [bytes(b) for b in blocks]
+    hdrs = []
+    if enc is None:
+        algo, items = E.CIPHER_NONE, blocks
+        hdrs = [b""] * len(blocks)
+    else:
+        algo, items = enc.algo, []
+        for b in blocks:
+            key = enc._rand(enc.keyLen)
+            cipherkey = enc.keyEncryptor.Encrypt(key)
+            nonce = enc._rand(12)
+            hdrs.append(bytes([len(cipherkey) >> 8, len(cipherkey) & 0xFF, len(nonce)]) + cipherkey + nonce)
+            items.append((key, nonce, b))
+    if not blocks:
+        return ([], []) if checksums else []
+    res = eng.store(algo, codec, items, crc=checksums)
+    objs, crcs = [], []
+    for k, h, (st, img, tag, crc, _) in zip(keys, hdrs, res):
+        if st != E.OK:  # no page CRCs were given to verify: the engine has no other per-block failure
+            raise CompressError("store %s: engine status %d" % (k, st))
+        obj = h + img + (tag or b"")
+        store.Put(k, obj)
+        objs.append(obj)
+        crcs.append(crc)
+    return (objs, crcs) if checksums else objs

@@ -28,6 +28,7 @@
 #define JFSX_HD static inline
 #include "jfsx_rsa.h"
 #include "jfsx_md5.h"
+#include "jfsx_store.h"
 
 using namespace jfsx;
 
@@ -428,6 +429,23 @@ struct jfsx_ctx {
     char *load_stage = nullptr;
     size_t load_scap = 0;
     hipEvent_t load_ev[4] = {};  // main-kernel timing of its Open and CRC stages
+    // jfsx_store_batch (run_store): likewise its own.  store_crc / store_aead /
+    // store_ct are the workspaces the page CRC stage, the Seal and the image
+    // CRC stage of a volume without a cipher plan into; store_d holds StoreBlk
+    // | ZDev | ZOut | StoreRes | sinks | the compressor's tables and scratch,
+    // store_h its pinned mirror (StoreBlk up, StoreRes down); store_stage the
+    // pages of a host batch and the compressor's output slots; store_img the
+    // packed images of a host batch (sized in phase B, from out_len).
+    Workspace store_crc, store_aead, store_ct;
+    char *store_d = nullptr;
+    size_t store_dcap = 0;
+    char *store_h = nullptr;
+    size_t store_hcap = 0;
+    char *store_stage = nullptr;
+    size_t store_scap = 0;
+    char *store_img = nullptr;
+    size_t store_icap = 0;
+    hipEvent_t store_ev[6] = {};  // main-kernel timing of its three stages
     double ms_total = 0;
     uint64_t launches = 0;
     BouncePool bounce;       // pinned staging of pageable caller memory (host calls)
@@ -1652,6 +1670,45 @@ int ensure_zstd_decode(jfsx_ctx *c, char **buf, size_t *cap, size_t base, int n,
     }
 }
 
+// What a compressor launch needs besides its descriptors, for run_codec and
+// run_store: `extra` bytes of device memory behind them -- LZ4's hash tables
+// (16 KiB per block), or the zstd compressor's ticket word (256 bytes) and
+// per-wave scratch -- and the zstd compressor's wave count.
+struct CompSetup {
+    bool zstd = false;
+    int zc_waves = 0;
+    bool zc_queue = false;
+    size_t extra = 0;
+};
+CompSetup comp_setup(const jfsx_ctx *c, bool zstd, int n) {
+    // zstd compression: persistent waves per CU (JFSX_ZC_WAVES overrides the
+    // default for A/B; LDS and VGPRs allow 16)
+    static const int zc_per_cu = getenv("JFSX_ZC_WAVES") ? std::max(1, std::min(16, atoi(getenv("JFSX_ZC_WAVES"))))
+                                                         : kZcWavesPerCu;
+    static const bool zc_queue = getenv("JFSX_ZC_QUEUE") && atoi(getenv("JFSX_ZC_QUEUE")) == 1;
+    CompSetup cs;
+    cs.zstd = zstd;
+    if (zstd) {
+        cs.zc_waves = std::min(n, c->ncu * zc_per_cu);
+        cs.zc_queue = zc_queue;
+        cs.extra = 256 + kZstdcScratch * (size_t)cs.zc_waves;  // per-wave scratch
+    } else {
+        cs.extra = kLz4TabBytes * (size_t)n;
+    }
+    return cs;
+}
+// tab: the cs.extra bytes
+void launch_compress(const jfsx_ctx *c, hipStream_t s, const CompSetup &cs, int n, const ZDev *dz, ZOut *dout,
+                     char *tab) {
+    if (!cs.zstd) {
+        launch_lz4_compress(s, n, c->ncu, dz, dout, (uint32_t *)tab);
+        return;
+    }
+    // JFSX_ZC_QUEUE=1: ticket-queue object assignment (A/B; the word before
+    // the scratch is the ticket counter)
+    launch_zstd_compress(s, n, cs.zc_waves, dz, dout, (uint8_t *)(tab + 256), cs.zc_queue ? (uint32_t *)tab : nullptr);
+}
+
 // The codec stages (jfsx_lz4.hip, jfsx_zstd.hip, jfsx_zstdc.hip): one wave per
 // object.  Host-memory batches are staged through the context's slot-0
 // staging buffer (inputs up, the out_len bytes of each output down).
@@ -1668,12 +1725,8 @@ int run_codec(jfsx_ctx *c, int n, jfsx_zblk *z, int mem, CodecOp op) {
     if (n == 0) return 0;
     int rc;
     Workspace &w = c->ws[0];
-    // zstd compression: persistent waves per CU (JFSX_ZC_WAVES overrides the
-    // default for A/B; LDS and VGPRs allow 16)
-    static const int zc_per_cu = getenv("JFSX_ZC_WAVES") ? std::max(1, std::min(16, atoi(getenv("JFSX_ZC_WAVES"))))
-                                                         : kZcWavesPerCu;
-    const int zc_waves = std::min(n, c->ncu * zc_per_cu);
-    static const bool zc_queue = getenv("JFSX_ZC_QUEUE") && atoi(getenv("JFSX_ZC_QUEUE")) == 1;
+    const bool comp = op == kLz4Comp || op == kZstdComp;
+    const CompSetup cs = comp ? comp_setup(c, op == kZstdComp, n) : CompSetup{};
     // zstd decompression: the decoder's waves and arenas (zstd_decode_waves,
     // ensure_zstd_decode: fewer waves, then the serial kernel, under memory
     // pressure)
@@ -1682,10 +1735,7 @@ int run_codec(jfsx_ctx *c, int n, jfsx_zblk *z, int mem, CodecOp op) {
     if (op == kZstdDecomp) {
         rc = ensure_zstd_decode(c, &w.d, &w.dcap, o_tab, n, &zd_waves);
     } else {
-        size_t extra = 0;
-        if (op == kLz4Comp) extra = kLz4TabBytes * (size_t)n;
-        else if (op == kZstdComp) extra = 256 + kZstdcScratch * (size_t)zc_waves;  // per-wave scratch
-        rc = ensure_dev(c, &w.d, &w.dcap, o_tab + extra);
+        rc = ensure_dev(c, &w.d, &w.dcap, o_tab + cs.extra);
     }
     if (rc) return rc;
     if ((rc = ensure_host(&w.h, &w.hcap, o_tab))) return rc;  // descriptors and results only
@@ -1716,19 +1766,14 @@ int run_codec(jfsx_ctx *c, int n, jfsx_zblk *z, int mem, CodecOp op) {
     launch_begin();
     switch (op) {
     case kLz4Comp:
-        launch_lz4_compress(s, n, c->ncu, dz, dout, (uint32_t *)(w.d + o_tab));
+    case kZstdComp:
+        launch_compress(c, s, cs, n, dz, dout, w.d + o_tab);
         break;
     case kLz4Decomp:
         launch_lz4_decompress(s, n, dz, dout);
         break;
     case kZstdDecomp:
         launch_zstd_decompress(s, n, dz, dout, (uint8_t *)(w.d + o_tab), zd_waves);
-        break;
-    case kZstdComp:
-        // JFSX_ZC_QUEUE=1: ticket-queue object assignment (A/B; the word
-        // before the scratch is the ticket counter)
-        launch_zstd_compress(s, n, zc_waves, dz, dout, (uint8_t *)(w.d + o_tab + 256),
-                             zc_queue ? (uint32_t *)(w.d + o_tab) : nullptr);
         break;
     }
     if (c->timing) HIP_OK(hipEventRecord(c->ev_k1[0], s));
@@ -2047,6 +2092,374 @@ int run_load(jfsx_ctx *c, int algo, int codec, int n, jfsx_lblk *blks, int crc_m
     return 0;
 }
 
+// ---------------------------------------------------------------------------
+// jfsx_store_batch: verify / checksum() -> compress -> Seal -> object checksum
+// of a batch of pages in one call (uploadStagingFile, cachedStore.upload,
+// store.put; cached_store.go:944-999, :371-413).  Two phases on the context's
+// stream (jfsx_store.hip has the order and the gate rule): the Seal's plan
+// needs the compressed lengths, so the per-block verdicts come back in the
+// middle (wait #1) and the host plans phase B from them.
+// ---------------------------------------------------------------------------
+int check_store_args(int algo, int codec, int n, const jfsx_sblk *blks, int crc_mode, int mem) {
+    if (algo != JFSX_AES256GCM && algo != JFSX_CHACHA20P1305 && algo != JFSX_CIPHER_NONE) return JFSX_EINVAL;
+    if (codec != JFSX_CODEC_LZ4 && codec != JFSX_CODEC_ZSTD) return JFSX_EINVAL;
+    // NONE, GEN, VERIFY, each with or without CT
+    if (crc_mode < 0 || (crc_mode & ~(3 | JFSX_CRC_CT)) || (crc_mode & 3) == 3) return JFSX_EINVAL;
+    if (mem != JFSX_MEM_DEVICE && mem != JFSX_MEM_HOST) return JFSX_EINVAL;
+    if (n < 0) return JFSX_EINVAL;
+    const bool aead = algo != JFSX_CIPHER_NONE, page_crc = (crc_mode & 3) != 0, ct = (crc_mode & JFSX_CRC_CT) != 0;
+    for (int i = 0; i < n; i++) {
+        const jfsx_sblk &b = blks[i];
+        if (b.reserved) return JFSX_EINVAL;
+        if ((b.len && !b.src) || !b.dst) return JFSX_EINVAL;  // an image is never empty
+        // run_codec's limits, then the ciphers' on the longest image (check_aead_args)
+        if (b.len > kLz4MaxInput) return JFSX_EINVAL;
+        const uint64_t bound = codec == JFSX_CODEC_ZSTD ? zstd_bound(b.len) : lz4_bound(b.len);
+        if (b.dst_cap < bound) return JFSX_EINVAL;
+        if (algo == JFSX_AES256GCM && bound > kGcmMaxLen) return JFSX_EINVAL;
+        if (algo == JFSX_CHACHA20P1305 && bound > kCpMaxLen) return JFSX_EINVAL;
+        if (page_crc && !b.crc) return JFSX_EINVAL;
+        if (ct && b.hdr_len && !b.hdr) return JFSX_EINVAL;
+        if (mem == JFSX_MEM_DEVICE) {
+            // jfsx_blk's rule where an AEAD or CRC kernel touches the buffer:
+            // the page CRC reads src, the Seal writes dst and the image CRC
+            // reads it; the compressors take any alignment
+            if (page_crc && b.len && !aligned16(b.src)) return JFSX_EINVAL;
+            if ((aead || ct) && !aligned16(b.dst)) return JFSX_EINVAL;
+            if (b.dst == b.src) return JFSX_EINVAL;  // the compressors do not run in place
+        }
+    }
+    return 0;
+}
+
+inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+struct StoreState {
+    bool host = false, aead = false, ct = false, zstd = false;
+    int page_mode = 0;       // JFSX_CRC_NONE / GEN / VERIFY of the pages
+    char *bounce = nullptr;  // pinned staging of the call's pageable pages (up) and images (down)
+    size_t bcap = 0;
+    CompSetup cs;
+    std::vector<uint64_t> cap;   // the codec's bound of every page length: the compressor's capacity
+    std::vector<size_t> poff;    // host: page i at store_stage + poff[i], and at bounce + poff[i]
+    std::vector<size_t> zoff;    // the compressor's output slot of block i at slots + zoff[i]
+    std::vector<size_t> ooff;    // host, phase B: image i at store_img + ooff[i], and at bounce + ooff[i]
+    char *slots = nullptr;       // null: the compressor writes to the callers' dst (device, no cipher)
+    std::vector<char> in_b, out_b;  // host: page i goes up / image i comes down through the bounce buffer
+    bool all_in = false, all_out = false;
+    size_t page_bytes = 0;
+    std::vector<jfsx_blk> pb;    // the page CRC stage's blocks
+    std::vector<jfsx_blk> sb;    // phase B: the Seal's / the image CRC stage's blocks, OK blocks only
+    std::vector<int> okidx;      // their indices in the batch
+    std::vector<uint8_t> ctcrc;  // their ciphertext segment CRCs (JFSX_CRC_CT)
+    size_t h_res = 0;            // offset of the downloaded StoreRes[n] in store_h
+};
+
+// Phase A: pages up, page CRCs, gate, compressor, verdicts down.
+int store_phase_a(jfsx_ctx *c, int n, const jfsx_sblk *blks, StoreState &st) {
+    hipStream_t s = c->stream;
+    const bool host = st.host;
+    st.cap.assign(n, 0);
+    st.poff.assign(n, 0);
+    st.zoff.assign(n, 0);
+    st.in_b.assign(n, 0);
+    st.out_b.assign(n, 0);
+    size_t page_bytes = 0, slot_bytes = 0, out_max = 0;
+    for (int i = 0; i < n; i++) {
+        st.cap[i] = st.zstd ? zstd_bound(blks[i].len) : lz4_bound(blks[i].len);
+        st.poff[i] = page_bytes;
+        page_bytes += align256(blks[i].len);
+        st.zoff[i] = slot_bytes;
+        slot_bytes += align256(st.cap[i]);
+        out_max += align16(st.cap[i]);
+    }
+    st.page_bytes = page_bytes;
+    const bool use_slots = host || st.aead;  // else the compressor writes the callers' dst
+    st.cs = comp_setup(c, st.zstd, n);
+    // device workspace of the store path
+    size_t off = 0;
+    const size_t o_sb = off; off = align256(off + sizeof(StoreBlk) * n);
+    const size_t up = off;  // the block records are uploaded from the pinned mirror
+    const size_t o_z = off; off = align256(off + sizeof(ZDev) * n);
+    const size_t o_zo = off; off = align256(off + sizeof(ZOut) * n);
+    const size_t o_res = off; off = align256(off + sizeof(StoreRes) * n);
+    const size_t o_sink = off; off = align256(off + kStoreSink * (size_t)n);
+    const size_t o_tab = off;
+    st.h_res = up;
+    int rc;
+    // every buffer of the phase before its first enqueue: growing one later
+    // would free what a stage already in flight uses
+    if ((rc = ensure_dev(c, &c->store_d, &c->store_dcap, o_tab + st.cs.extra))) return rc;
+    if ((rc = ensure_host(&c->store_h, &c->store_hcap, up + sizeof(StoreRes) * n))) return rc;
+    const size_t stage_need = (host ? page_bytes : 0) + (use_slots ? slot_bytes : 0);
+    if (stage_need && (rc = ensure_dev(c, &c->store_stage, &c->store_scap, stage_need))) return rc;
+    char *d = c->store_d, *h = c->store_h, *stage = c->store_stage;
+    st.slots = use_slots ? stage + (host ? page_bytes : 0) : nullptr;
+    // host: which pages and images go through the bounce pool (pageable caller
+    // memory).  One buffer serves both directions: the stream has finished the
+    // uploads out of it at wait #1, before phase B downloads into it.
+    bool any_in = false, any_out = false;
+    st.all_in = st.all_out = host;
+    if (host) {
+        for (int i = 0; i < n; i++) {
+            if (blks[i].len) {
+                st.in_b[i] = !host_pinned(blks[i].src, blks[i].len);
+                st.all_in = st.all_in && st.in_b[i];
+                any_in = any_in || st.in_b[i];
+            }
+            st.out_b[i] = !host_pinned(blks[i].dst, st.cap[i]);
+            st.all_out = st.all_out && st.out_b[i];
+            any_out = any_out || st.out_b[i];
+        }
+        const size_t need = std::max(any_in ? page_bytes : 0, any_out ? out_max : 0);
+        if (need) {
+            if (!(st.bounce = bounce_get(c, need, &st.bcap))) return JFSX_ENOMEM;
+            std::vector<std::pair<char *, const char *>> cp;
+            std::vector<size_t> cl;
+            for (int i = 0; i < n; i++)
+                if (st.in_b[i]) {
+                    cp.push_back({st.bounce + st.poff[i], (const char *)blks[i].src});
+                    cl.push_back(blks[i].len);
+                    c->bounce.bytes_in += blks[i].len;
+                }
+            par_copy(cp, cl);
+        }
+    }
+    // block records; the page CRC stage's blocks
+    StoreBlk *hs = (StoreBlk *)(h + o_sb);
+    st.pb.assign(st.page_mode ? n : 0, jfsx_blk{});
+    for (int i = 0; i < n; i++) {
+        const jfsx_sblk &b = blks[i];
+        hs[i].src = !b.len ? nullptr : host ? (const uint8_t *)(stage + st.poff[i]) : (const uint8_t *)b.src;
+        hs[i].dst = use_slots ? (uint8_t *)(st.slots + st.zoff[i]) : (uint8_t *)b.dst;
+        hs[i].sink = (uint8_t *)(d + o_sink + kStoreSink * (size_t)i);
+        hs[i].len = b.len;
+        hs[i].cap = st.cap[i];
+        if (st.page_mode) {
+            jfsx_blk &k = st.pb[i];
+            memset(&k, 0, sizeof(k));
+            k.src = hs[i].src;
+            k.len = b.len;
+            k.crc = b.crc;  // host: rides the stage's descriptor upload (VERIFY) / result download (GEN)
+        }
+    }
+    // 1. upload: the records, and every page once
+    HIP_OK(hipMemcpyAsync(d + o_sb, h + o_sb, sizeof(StoreBlk) * n, hipMemcpyHostToDevice, s));
+    if (host) {
+        if (st.all_in && page_bytes) {
+            HIP_OK(hipMemcpyAsync(stage, st.bounce, page_bytes, hipMemcpyHostToDevice, s));
+        } else {
+            for (int i = 0; i < n; i++)
+                if (blks[i].len)
+                    HIP_OK(hipMemcpyAsync(stage + st.poff[i],
+                                          st.in_b[i] ? st.bounce + st.poff[i] : (const char *)blks[i].src,
+                                          blks[i].len, hipMemcpyHostToDevice, s));
+        }
+    }
+    // 2. checksum() of every page, or its verify; the BlkOut[n] stays on the device
+    const BlkOut *verified = nullptr;
+    if (st.page_mode) {
+        if ((rc = enqueue_crc(c, c->store_crc, s, c->store_ev[0], c->store_ev[1], n, st.pb.data(), st.page_mode,
+                              nullptr, nullptr, false, host)))
+            return rc;
+        if (st.page_mode == JFSX_CRC_VERIFY) verified = (const BlkOut *)c->store_crc.dout;
+    }
+    // 3. the gate, 4. the compressor: it sees a block only through the gate's descriptor
+    const StoreBlk *ds = (const StoreBlk *)(d + o_sb);
+    ZDev *dz = (ZDev *)(d + o_z);
+    ZOut *dzo = (ZOut *)(d + o_zo);
+    launch_begin();
+    launch_store_gate(s, n, ds, verified, dz, dzo);
+    launch_compress(c, s, st.cs, n, dz, dzo, d + o_tab);
+    // 5. verdicts, and their download
+    launch_store_verdict(s, n, ds, verified, dzo, (StoreRes *)(d + o_res));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(h + st.h_res, d + o_res, sizeof(StoreRes) * n, hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
+// Phase B, after wait #1: the Seal (or, without a cipher, the image CRCs)
+// planned from out_len over the OK blocks, then every download.
+int store_phase_b(jfsx_ctx *c, int algo, int n, const jfsx_sblk *blks, StoreState &st) {
+    hipStream_t s = c->stream;
+    const bool host = st.host;
+    const StoreRes *hr = (const StoreRes *)(c->store_h + st.h_res);
+    st.ooff.assign(n, 0);
+    size_t out_bytes = 0;
+    uint64_t ct_words = 0;
+    for (int i = 0; i < n; i++) {
+        if (hr[i].status == jfsx_store::kBroken) return JFSX_EIO;  // no Seal is planned from such a length
+        if (hr[i].status != JFSX_OK) continue;
+        st.okidx.push_back(i);
+        st.ooff[i] = out_bytes;
+        out_bytes += align16(hr[i].out_len);
+        ct_words += nseg_of(hr[i].out_len);
+    }
+    const int m = (int)st.okidx.size();
+    int rc;
+    if (host && st.aead && out_bytes && (rc = ensure_dev(c, &c->store_img, &c->store_icap, out_bytes))) return rc;
+    if (st.ct) st.ctcrc.assign(4 * ct_words, 0);
+    // 6. the Seal out of the compressor's slots, or the image CRCs where they lie
+    if (m && (st.aead || st.ct)) {
+        st.sb.assign(m, jfsx_blk{});
+        uint64_t cw = 0;
+        for (int k = 0; k < m; k++) {
+            const int i = st.okidx[k];
+            jfsx_blk &a = st.sb[k];
+            memset(&a, 0, sizeof(a));
+            const void *img = st.slots ? (const void *)(st.slots + st.zoff[i]) : blks[i].dst;
+            a.src = img;
+            a.len = hr[i].out_len;
+            if (st.aead) {
+                memcpy(a.key, blks[i].key, 32);
+                memcpy(a.nonce, blks[i].nonce, 12);
+                a.dst = host ? (void *)(c->store_img + st.ooff[i]) : blks[i].dst;
+            }
+            if (st.ct) a.crc = st.ctcrc.data() + 4 * cw;  // host arrays: they ride the result download
+            cw += nseg_of(a.len);
+        }
+        if (st.aead)
+            rc = enqueue_aead(c, c->store_aead, s, c->store_ev[2], c->store_ev[3], algo, false, m, st.sb.data(),
+                              st.ct ? (JFSX_CRC_GEN | JFSX_CRC_CT) : JFSX_CRC_NONE, nullptr, nullptr, true, nullptr,
+                              nullptr, st.ct);
+        else
+            rc = enqueue_crc(c, c->store_ct, s, c->store_ev[4], c->store_ev[5], m, st.sb.data(), JFSX_CRC_GEN, nullptr,
+                             nullptr, true, true);
+        if (rc) return rc;
+    }
+    // 7. downloads: the page CRC stage's results (host GEN: the CRC words behind them), the images
+    if (st.page_mode) {
+        Workspace &w = c->store_crc;
+        HIP_OK(hipMemcpyAsync(w.h + w.res_off, w.dout, w.down, hipMemcpyDeviceToHost, s));
+    }
+    if (host && m) {
+        if (st.aead && st.all_out) {
+            HIP_OK(hipMemcpyAsync(st.bounce, c->store_img, out_bytes, hipMemcpyDeviceToHost, s));
+        } else {
+            for (int i : st.okidx) {
+                const char *img = st.aead ? c->store_img + st.ooff[i] : st.slots + st.zoff[i];
+                HIP_OK(hipMemcpyAsync(st.out_b[i] ? st.bounce + st.ooff[i] : (char *)blks[i].dst, img, hr[i].out_len,
+                                      hipMemcpyDeviceToHost, s));
+            }
+        }
+    }
+    return 0;
+}
+
+// Under c->mu for the whole call, as device batches are; the arguments have
+// passed check_store_args and n > 0.
+int run_store(jfsx_ctx *c, int algo, int codec, int n, jfsx_sblk *blks, int crc_mode, int mem) {
+    int rc = 0;
+    StoreState st;
+    st.host = mem == JFSX_MEM_HOST;
+    st.aead = algo != JFSX_CIPHER_NONE;
+    st.ct = (crc_mode & JFSX_CRC_CT) != 0;
+    st.zstd = codec == JFSX_CODEC_ZSTD;
+    st.page_mode = crc_mode & 3;
+    // a wait ends a phase; after an enqueue error nothing of the call is left in flight
+    auto wait = [&](const char *what) {
+        const hipError_t se = hipStreamSynchronize(c->stream);
+        if (!rc && se != hipSuccess) {
+            note_hip_error(se, __FILE__, __LINE__, what);
+            rc = JFSX_EIO;
+        }
+    };
+    rc = store_phase_a(c, n, blks, st);
+    wait("hipStreamSynchronize(store, wait #1)");
+    if (!rc) {
+        rc = store_phase_b(c, algo, n, blks, st);
+        wait("hipStreamSynchronize(store, wait #2)");
+    }
+    // the stages' results (tags, ciphertext CRC words, page CRC words) and main-kernel times
+    Workspace *ws[3] = {&c->store_crc, &c->store_aead, &c->store_ct};
+    jfsx_blk *wb[3] = {st.pb.data(), st.sb.data(), st.sb.data()};
+    for (int k = 0; k < 3; k++) {
+        Workspace &w = *ws[k];
+        if (!rc && w.n) {
+            rc = finish_aead(c, w, c->store_ev[2 * k], c->store_ev[2 * k + 1], k != 1, wb[k]);
+        } else {
+            w.n = 0;
+            w.nt = 0;
+            w.timed = false;
+            w.crc_back = false;
+        }
+    }
+    if (!rc) {
+        const StoreRes *hr = (const StoreRes *)(c->store_h + st.h_res);
+        std::vector<std::pair<char *, const char *>> cp;
+        std::vector<size_t> cl;
+        for (int i = 0; i < n; i++) {
+            jfsx_sblk &b = blks[i];
+            b.status = hr[i].status;
+            b.out_len = hr[i].out_len;
+            b.crc_bad_seg = hr[i].bad_seg;
+            b.crc_got = hr[i].got;
+            b.crc_expect = hr[i].expect;
+            b.obj_crc = 0;
+            memset(b.tag, 0, 16);
+        }
+        uint64_t cw = 0;
+        for (size_t k = 0; k < st.okidx.size(); k++) {
+            jfsx_sblk &b = blks[st.okidx[k]];
+            if (st.aead) memcpy(b.tag, st.sb[k].tag, 16);
+            if (st.ct) {
+                // 8. generateChecksum(hdr || image || tag) from the segment CRCs
+                const uint8_t *seg = st.ctcrc.data() + 4 * cw;
+                if (st.aead) {
+                    (void)jfsx_object_crc32c(b.hdr, b.hdr_len, seg, b.out_len, b.tag, &b.obj_crc);
+                } else {
+                    uint32_t crc = jfsx_crc32c_update(0, b.hdr, b.hdr_len);
+                    for (uint64_t j = 0; j < nseg_of(b.out_len); j++) {
+                        const uint8_t *p = seg + 4 * j;
+                        const uint32_t cj = (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3];
+                        crc = jfsx_crc32c_combine(crc, cj, std::min<uint64_t>(kSeg, b.out_len - j * kSeg));
+                    }
+                    b.obj_crc = crc;
+                }
+                cw += nseg_of(b.out_len);
+            }
+            if (st.host && st.out_b[st.okidx[k]]) {
+                cp.push_back({(char *)b.dst, st.bounce + st.ooff[st.okidx[k]]});
+                cl.push_back(b.out_len);
+                c->bounce.bytes_out += b.out_len;
+            }
+        }
+        par_copy(cp, cl);
+    }
+    if (st.bounce) bounce_put(c, st.bounce, st.bcap);
+    if (rc) return rc;
+    // jfsx_ctx_metrics: what the separate calls would have counted
+    std::lock_guard<std::mutex> g(c->stat_mu);
+    jfsx_metrics &m = c->met;
+    uint64_t &c_blocks = st.zstd ? m.zstdc_blocks : m.lz4c_blocks, &c_in = st.zstd ? m.zstdc_in : m.lz4c_in;
+    uint64_t &c_out = st.zstd ? m.zstdc_out : m.lz4c_out;
+    const bool ct_launch = st.ct && !st.aead && !st.okidx.empty();  // the image CRC stage: a CRC call of its own
+    if (st.page_mode) m.crc_batches++;
+    if (ct_launch) m.crc_batches++;
+    if (st.aead && !st.okidx.empty()) m.seal_batches++;
+    for (int i = 0; i < n; i++) {
+        const jfsx_sblk &b = blks[i];
+        if (st.page_mode) {
+            m.crc_ranges++;
+            m.crc_bytes += b.len;
+            m.crc_fail += b.status == JFSX_ECRC;
+        }
+        if (b.status != JFSX_OK) continue;  // the block passed the gate
+        c_blocks++;
+        c_in += b.len;
+        c_out += b.out_len;
+        if (st.aead) {
+            m.seal_blocks++;
+            m.seal_bytes += b.out_len;
+        }
+        if (ct_launch) {
+            m.crc_ranges++;
+            m.crc_bytes += b.out_len;
+        }
+    }
+    return 0;
+}
+
 }  // namespace
 
 namespace jfsx {
@@ -2202,6 +2615,13 @@ int jfsx_ctx_open(int device, uint32_t flags, jfsx_ctx **out) {
             return JFSX_EIO;
         }
     }
+    for (hipEvent_t &e : c->store_ev) {
+        if (hipEventCreate(&e) != hipSuccess) {
+            e = nullptr;
+            jfsx_ctx_close(c);
+            return JFSX_EIO;
+        }
+    }
     for (PipeSlot &p : c->pipe) {
         if (hipEventCreateWithFlags(&p.ev_in, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&p.ev_comp, hipEventDisableTiming) != hipSuccess ||
@@ -2246,6 +2666,16 @@ int jfsx_ctx_close(jfsx_ctx *c) {
     if (c->load_stage) (void)hipFree(c->load_stage);
     if (c->load_h) (void)hipHostFree(c->load_h);
     for (hipEvent_t e : c->load_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (Workspace *w : {&c->store_crc, &c->store_aead, &c->store_ct}) {
+        if (w->d) (void)hipFree(w->d);
+        if (w->h) (void)hipHostFree(w->h);
+    }
+    if (c->store_d) (void)hipFree(c->store_d);
+    if (c->store_stage) (void)hipFree(c->store_stage);
+    if (c->store_img) (void)hipFree(c->store_img);
+    if (c->store_h) (void)hipHostFree(c->store_h);
+    for (hipEvent_t e : c->store_ev)
         if (e) (void)hipEventDestroy(e);
     for (auto &kv : c->bounce.idle) {
         forget_pinned(kv.second);
@@ -2622,6 +3052,17 @@ int jfsx_load_batch(jfsx_ctx *c, int algo, int codec, int n, jfsx_lblk *blks, in
     CtxScope es_(c);
     HIP_OK(hipSetDevice(c->device));
     return run_load(c, algo, codec, n, blks, crc_mode, mem);
+}
+
+int jfsx_store_batch(jfsx_ctx *c, int algo, int codec, int n, jfsx_sblk *blks, int crc_mode, int mem) {
+    if (!c || (n > 0 && !blks)) return JFSX_EINVAL;
+    // argument errors before the context's device is touched
+    const int rc = check_store_args(algo, codec, n, blks, crc_mode, mem);
+    if (rc || n == 0) return rc;
+    std::lock_guard<std::mutex> g(c->mu);
+    CtxScope es_(c);
+    HIP_OK(hipSetDevice(c->device));
+    return run_store(c, algo, codec, n, blks, crc_mode, mem);
 }
 
 int jfsx_checksum(jfsx_ctx *c, const void *data, uint64_t len, uint8_t *out) {

@@ -332,6 +332,30 @@ void launch_load_gate(hipStream_t s, int n, const LoadBlk *lb, const BlkOut *ope
 // use_fallback: ZOut.fallback is meaningful (the block-parallel zstd decoder ran)
 void launch_load_finish(hipStream_t s, int n, int wipe_groups, const LoadBlk *lb, const BlkOut *opened,
                         const ZOut *zo, bool use_fallback, bool crc_gen, LoadRes *res);
+// One-call block store (jfsx_store.hip): the kernels around the compressor of
+// jfsx_store_batch.  StoreBlk: src = the page, dst = where the compressor
+// writes (cap bytes, the codec's bound of len), sink = kStoreSink bytes of
+// engine scratch of the block's own (device addresses).  verified = the page
+// CRC stage's BlkOut[n] with JFSX_CRC_VERIFY, else null.
+constexpr uint64_t kStoreSink = 16;
+struct StoreBlk {
+    const uint8_t *src;
+    uint8_t *dst;
+    uint8_t *sink;
+    uint64_t len, cap;
+};
+struct StoreRes {  // copied back to the host (wait #1)
+    uint64_t out_len;
+    int32_t status;  // JFSX_OK / JFSX_ECRC / jfsx_store::kBroken
+    int32_t bad_seg;
+    uint32_t got, expect;
+};
+// ZDev[n] for the compressor: {src, dst, len, cap}, or {null, sink, 0,
+// kStoreSink} for a block whose page failed its CRCs; ZOut[n] initialised
+void launch_store_gate(hipStream_t s, int n, const StoreBlk *sb, const BlkOut *verified, ZDev *z, ZOut *zo);
+// the verdict of every block (jfsx_store.h) into res
+void launch_store_verdict(hipStream_t s, int n, const StoreBlk *sb, const BlkOut *verified, const ZOut *zo,
+                          StoreRes *res);
 // batched RSA-OAEP unwrap (jfsx_rsa.hip): key = device jfsx_rsa::Key
 void async_detach(jfsx_ctx *c);  // jfsx_agg.cpp
 void launch_rsa_unwrap(hipStream_t s, const void *key, int n, const uint8_t *ct, uint32_t *mh, uint8_t *em,

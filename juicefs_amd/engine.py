@@ -27,8 +27,8 @@ EOF = 3  # jfsx_cache_verify: short read
 EFORMAT = 4  # malformed LZ4 block / zstd frame (the library's error)
 EDSTSIZE = 5  # zstd: the output does not fit in dst_cap
 ESHORT = 6  # jfsx_load_batch: the image decoded to fewer bytes than the page ("read %s fully")
-CIPHER_NONE = -1  # jfsx_load_batch algo: the volume is not encrypted
-CODEC_LZ4, CODEC_ZSTD = 1, 2  # jfsx_load_batch codec
+CIPHER_NONE = -1  # jfsx_load_batch / jfsx_store_batch algo: the volume is not encrypted
+CODEC_LZ4, CODEC_ZSTD = 1, 2  # jfsx_load_batch / jfsx_store_batch codec
 EINVAL, ENODEV, EIO, ENOMEM, EMISFORMED, EAGAIN = -22, -19, -5, -12, -74, -11
 SEG = 32 << 10
 
@@ -54,7 +54,7 @@ EXPORTS = [
     "jfsx_agg_data_encrypt", "jfsx_agg_data_decrypt",
     "jfsx_data_encrypt_ex", "jfsx_data_decrypt_ex", "jfsx_agg_data_encrypt_ex", "jfsx_agg_data_decrypt_ex",
     "jfsx_file_checksum_span", "jfsx_file_checksum_batch", "jfsx_file_checksum_fold",
-    "jfsx_load_batch",
+    "jfsx_load_batch", "jfsx_store_batch",
 ]
 
 
@@ -116,6 +116,17 @@ class jfsx_lblk(ctypes.Structure):
         ("tag", ctypes.c_uint8 * 16), ("src", ctypes.c_void_p), ("src_len", ctypes.c_uint64),
         ("dst", ctypes.c_void_p), ("len", ctypes.c_uint64), ("crc", ctypes.c_void_p),
         ("out_len", ctypes.c_uint64), ("status", ctypes.c_int32), ("codec_info", ctypes.c_int32),
+    ]
+
+
+class jfsx_sblk(ctypes.Structure):
+    _fields_ = [
+        ("key", ctypes.c_uint8 * 32), ("nonce", ctypes.c_uint8 * 12), ("reserved", ctypes.c_uint32),
+        ("tag", ctypes.c_uint8 * 16), ("src", ctypes.c_void_p), ("len", ctypes.c_uint64),
+        ("dst", ctypes.c_void_p), ("dst_cap", ctypes.c_uint64), ("crc", ctypes.c_void_p),
+        ("hdr", ctypes.c_void_p), ("hdr_len", ctypes.c_uint32), ("obj_crc", ctypes.c_uint32),
+        ("out_len", ctypes.c_uint64), ("status", ctypes.c_int32), ("crc_bad_seg", ctypes.c_int32),
+        ("crc_got", ctypes.c_uint32), ("crc_expect", ctypes.c_uint32),
     ]
 
 
@@ -238,6 +249,7 @@ def load_library(path=LIB_PATH):
             "jfsx_agg_zstd_compress": (I, [P, ctypes.POINTER(jfsx_zblk), I]),
             "jfsx_mctx_zstd_compress_batch": (I, [P, I, ctypes.POINTER(jfsx_zblk), I]),
             "jfsx_load_batch": (I, [P, I, I, I, ctypes.POINTER(jfsx_lblk), I, I]),
+            "jfsx_store_batch": (I, [P, I, I, I, ctypes.POINTER(jfsx_sblk), I, I]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -649,6 +661,70 @@ class Engine:
         self.load_info = [(arr[i].out_len, arr[i].codec_info) for i in range(cnt)]
         return [(arr[i].status, page[:n].tobytes(), cbuf.tobytes() if crc else None)
                 for i, (_, page, cbuf, n) in enumerate(keep)]
+
+    # -- one-call block store (jfsx_store_batch) ---------------------------
+    @staticmethod
+    def make_sblocks(specs):
+        """specs: iterable of dicts with src, len, dst, dst_cap, [key, nonce] (a
+        cipher), [crc] (CRC_GEN / CRC_VERIFY), [hdr, hdr_len] (CRC_CT; host
+        memory); pointers as ints."""
+        specs = list(specs)
+        arr = (jfsx_sblk * max(len(specs), 1))()
+        for i, s in enumerate(specs):
+            b = arr[i]
+            if s.get("key") is not None:
+                ctypes.memmove(b.key, bytes(s["key"]), 32)
+                ctypes.memmove(b.nonce, bytes(s["nonce"]), 12)
+            b.src, b.len = s.get("src"), s["len"]
+            b.dst, b.dst_cap = s.get("dst"), s["dst_cap"]
+            b.crc = s.get("crc")
+            b.hdr, b.hdr_len = s.get("hdr"), s.get("hdr_len", 0)
+        return arr, len(specs)
+
+    def store_batch(self, algo, codec, sblks, n, crc_mode=CRC_GEN, mem=MEM_DEVICE):
+        """The staged re-read's verify (or checksum()), cachedStore.upload's
+        Compress, Encrypt and the object checksum of n pages in one call;
+        per-block results in sblks[i].status (OK / ECRC), .out_len, .tag,
+        .obj_crc and the crc_* fields."""
+        self._check(self.L.jfsx_store_batch(self.ctx, algo, codec, n, sblks, crc_mode, mem), "jfsx_store_batch")
+
+    def store(self, algo, codec, items, crc=True, verify=None, headers=None):
+        """Host bytes in, host bytes out.  items: (key, nonce, page) per block
+        with a cipher, the page itself with CIPHER_NONE.  crc: checksum() of
+        every page comes back; verify: the pages' CRC arrays to check instead
+        (the staged upload); headers: the object header of each block, which
+        asks for the object checksum.  Returns (status, image, tag or None,
+        page crc bytes or None, obj_crc or None) per block; self.store_info
+        holds (crc_bad_seg, crc_got, crc_expect) per block."""
+        bound = lz4_bound if codec == CODEC_LZ4 else zstd_bound
+        specs, keep = [], []
+        for i, it in enumerate(items):
+            key, nonce, page = (None, None, it) if algo == CIPHER_NONE else it
+            src = _u8(page)
+            cap = int(bound(src.size))
+            dst = np.empty(cap, np.uint8)
+            if verify is not None:
+                cbuf = _u8(verify[i])
+            else:
+                cbuf = np.empty(4 * max(1, -(-int(src.size) // SEG)), np.uint8)
+            hdr = _u8(headers[i]) if headers is not None else None
+            keep.append((src, dst, cbuf, hdr))
+            specs.append({"key": key, "nonce": nonce, "src": src.ctypes.data if src.size else None, "len": src.size,
+                          "dst": dst.ctypes.data, "dst_cap": cap,
+                          "crc": cbuf.ctypes.data if (crc or verify is not None) else None,
+                          "hdr": hdr.ctypes.data if hdr is not None and hdr.size else None,
+                          "hdr_len": hdr.size if hdr is not None else 0})
+        mode = CRC_VERIFY if verify is not None else CRC_GEN if crc else CRC_NONE
+        if headers is not None:
+            mode |= CRC_CT
+        arr, cnt = self.make_sblocks(specs)
+        self.store_batch(algo, codec, arr, cnt, mode, MEM_HOST)
+        self.store_info = [(arr[i].crc_bad_seg, arr[i].crc_got, arr[i].crc_expect) for i in range(cnt)]
+        return [(arr[i].status, dst[:arr[i].out_len].tobytes(),
+                 bytes(arr[i].tag) if algo != CIPHER_NONE else None,
+                 cbuf.tobytes() if (crc or verify is not None) else None,
+                 arr[i].obj_crc if headers is not None else None)
+                for i, (_, dst, cbuf, _) in enumerate(keep)]
 
     # -- asynchronous batches (jfsx_*_async + jfsx_wait) ------------------
     def _ticket(self, fn, what, *args):
