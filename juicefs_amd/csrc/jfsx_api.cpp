@@ -238,7 +238,12 @@ uint32_t crc_mulmod_h(uint32_t a, uint32_t b) {
     return p;
 }
 
-void make_crc_tables(std::vector<uint32_t> &crc, std::vector<uint32_t> &crcx) {
+// crcb (nullable): the composed tables of gcm_main's two-row loop, which
+// carries B = x^8064 * A (the lane CRC already shifted across the 1008-byte
+// gap to its next piece): TT_0..15, TT_k[v] = x^8064 * U_k[v] (16 x 256
+// dwords), then the 64 lane constants xlB[l] = xl[l] * x^-8064 that bring a
+// B-form state to the segment end (xlB[63] = x^-8064 itself)
+void make_crc_tables(std::vector<uint32_t> &crc, std::vector<uint32_t> &crcx, std::vector<uint32_t> *crcb = nullptr) {
     uint32_t T[256];
     for (uint32_t i = 0; i < 256; i++) {
         uint32_t c = i;
@@ -278,6 +283,17 @@ void make_crc_tables(std::vector<uint32_t> &crc, std::vector<uint32_t> &crcx) {
     // x^(8 * 1024 k), k = 1..31: whole-row shifts (crc_xpow8_fast, jfsx_internal.h)
     for (int k = 1; k < 32; k++) crcx[96 + k] = xpow8(1024 * (uint64_t)k);
     for (int l = 0; l < 64; l++) crcx[128 + l] = xpow8(64 * (63 - l));
+    if (crcb) {
+        crcb->assign(16 * 256 + 64, 0);
+        for (int i = 0; i < 16 * 256; i++) (*crcb)[i] = crc_mulmod_h(x1008, crc[i]);
+        // P(0) = 1, so x * ((P - 1) / x) = 1 mod P: x^-1 is P without its
+        // constant term, divided by x (one bit to the left in this bit order,
+        // x^32 / x landing on bit 0); x^-8064 by square and multiply
+        uint32_t sq = ((kCrcPoly & 0x7fffffffu) << 1) | 1u, inv = 0x80000000u;
+        for (uint32_t n = 8 * 1008; n; n >>= 1, sq = crc_mulmod_h(sq, sq))
+            if (n & 1) inv = crc_mulmod_h(sq, inv);
+        for (int l = 0; l < 64; l++) (*crcb)[16 * 256 + l] = crc_mulmod_h(crcx[l], inv);
+    }
 }
 
 // crc_chunks_k's chunk-end multiplies (jfsx_crc.hip): the lane CRC of the
@@ -2578,12 +2594,12 @@ int jfsx_ctx_open(int device, uint32_t flags, jfsx_ctx **out) {
         jfsx_ctx_close(c);
         return JFSX_EIO;
     }
-    std::vector<uint32_t> aes, crc, crcx;
+    std::vector<uint32_t> aes, crc, crcx, crcb;
     make_aes_table(aes);
-    make_crc_tables(crc, crcx);
+    make_crc_tables(crc, crcx, &crcb);
     std::vector<uint32_t> cmul;
     make_crc_chunk_mul(cmul, &c->k512);
-    const size_t nbytes = 4 * (aes.size() + crc.size() + crcx.size() + cmul.size());
+    const size_t nbytes = 4 * (aes.size() + crc.size() + crcx.size() + cmul.size() + crcb.size());
     if (hipMalloc((void **)&c->d_tab, nbytes) != hipSuccess) {
         c->d_tab = nullptr;
         jfsx_ctx_close(c);  // the streams made above
@@ -2593,6 +2609,7 @@ int jfsx_ctx_open(int device, uint32_t flags, jfsx_ctx **out) {
     all.insert(all.end(), aes.begin(), aes.end());
     all.insert(all.end(), crc.begin(), crc.end());
     all.insert(all.end(), crcx.begin(), crcx.end());
+    all.insert(all.end(), crcb.begin(), crcb.end());  // right behind crcx: the kernels reach it from tabs.crcx
     all.insert(all.end(), cmul.begin(), cmul.end());
     if (hipMemcpy(c->d_tab, all.data(), nbytes, hipMemcpyHostToDevice) != hipSuccess) {
         jfsx_ctx_close(c);
@@ -2601,7 +2618,7 @@ int jfsx_ctx_open(int device, uint32_t flags, jfsx_ctx **out) {
     c->tabs.aes = c->d_tab;
     c->tabs.crc = c->d_tab + aes.size();
     c->tabs.crcx = c->d_tab + aes.size() + crc.size();
-    c->d_chunk_mul = c->tabs.crcx + crcx.size();
+    c->d_chunk_mul = c->tabs.crcx + crcx.size() + crcb.size();
     for (int k = 0; k < kRing; k++) {
         if (hipEventCreate(&c->ev_k0[k]) != hipSuccess || hipEventCreate(&c->ev_k1[k]) != hipSuccess) {
             jfsx_ctx_close(c);
@@ -3720,6 +3737,16 @@ int jfsx_debug_tables(uint32_t *aes, uint32_t *crc, uint32_t *crcx) {
     if (aes) memcpy(aes, a.data(), 4 * a.size());
     if (crc) memcpy(crc, c.data(), 4 * c.size());
     if (crcx) memcpy(crcx, x.data(), 4 * x.size());
+    return 0;
+}
+
+// The composed CRC tables of gcm_main's two-row loop (make_crc_tables): tt
+// 4096 dwords (TT_0..15), xlb 64.  Not part of the ABI (undeclared in jfsx.h).
+int jfsx_debug_crc_composed(uint32_t *tt, uint32_t *xlb) {
+    std::vector<uint32_t> c, x, b;
+    make_crc_tables(c, x, &b);
+    if (tt) memcpy(tt, b.data(), 4 * 4096);
+    if (xlb) memcpy(xlb, b.data() + 4096, 4 * 64);
     return 0;
 }
 

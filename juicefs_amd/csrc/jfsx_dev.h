@@ -48,8 +48,8 @@ __device__ __forceinline__ uint32_t crc_piece(const char *lds, uint32_t A, uint3
 // piece's step are indexed by the data words p1..p3 alone, so where the data
 // is in registers long before the step (the two-row loop of gcm_main with the
 // CRC over the loaded side) K of them, tables 4 .. 3 + K, are gathered from the
-// device image of the tables (DevTables::crc) instead of its LDS copy: issued
-// early, XOR-folded as they return, and handed to crc_piece_l1 as L.  A lookup
+// device image of the tables instead of its LDS copy: issued early,
+// XOR-folded as they return, and handed to the step (crc_piece_b) as L.  A lookup
 // is one address op and one global_load_dword (SGPR base, the table's offset
 // in the instruction); it takes no LDS cycle.
 typedef __attribute__((address_space(1))) const uint32_t gcu32;
@@ -84,20 +84,40 @@ __device__ __forceinline__ void crc_l1_issue(const CrcL1Base &g, const uint4 (&d
     }
 }
 
-// crc_piece with the lookups of tables 4 .. 3 + K (K = 4, 8 or 12) already
-// summed in L
-template <uint32_t CB, int K, int S = 16>
-__device__ __forceinline__ uint32_t crc_piece_l1(const char *lds, uint32_t A, uint32_t p0, uint32_t p1, uint32_t p2,
-                                                 uint32_t p3, uint32_t L) {
-    static_assert(K == 4 || K == 8 || K == 12, "whole data words only");
-#define X3(a, b, c) __builtin_amdgcn_bitop3_b32((a), (b), (c), 0x96)
-    uint32_t s = S < 0 ? A : X3(CRC_T(S, A, 0), CRC_T(S + 1, A, 1), CRC_T(S + 2, A, 2)) ^ CRC_T(S + 3, A, 3);
-    uint32_t q = p0 ^ s;
-    uint32_t r = X3(X3(CRC_T(0, q, 0), CRC_T(1, q, 1), CRC_T(2, q, 2)), CRC_T(3, q, 3), L);
-    if constexpr (K < 8) r = X3(r, X3(CRC_T(8, p2, 0), CRC_T(9, p2, 1), CRC_T(10, p2, 2)), CRC_T(11, p2, 3));
-    if constexpr (K < 12) r = X3(X3(r, CRC_T(12, p3, 0), CRC_T(13, p3, 1)), CRC_T(14, p3, 2), CRC_T(15, p3, 3));
-#undef X3
-    return r;
+// B form.  The two-row loop of gcm_main carries B = x^8064 * A, the lane CRC
+// already shifted across the 1008-byte gap to the lane's next piece, so the
+// shift is no lookup generation of its own: with the composed tables
+// TT_k[v] = x^8064 * U_k[v] (make_crc_tables) the step is
+// B' = sum_{k<4} TT_k[byte k of (p0 ^ B)] ^ sum_{k>=4} TT_k[data byte],
+// the twelve data-only terms gathered through the L1 (L) as before.  TT_0..3
+// are staged in LDS at CB.  0 is the same in both forms; a B-form state comes
+// back through xlB[l] = xl[l] * x^-8064 at a segment end (xlB[63] = x^-8064),
+// or enters the next piece through crc_piece's no-shift entry (S < 0).
+constexpr uint32_t kCrcbXl = 16 * 256;  // dword offset of xlB in the composed image
+__device__ __forceinline__ const uint32_t *crc_composed(const DevTables &tab) { return tab.crcx + kCrcxDwords; }
+// xlB[l], loaded where it is used (once per segment): the address is made
+// there too, not kept in registers through the row loop
+__device__ __forceinline__ uint32_t crc_xlb(const DevTables &tab, uint32_t l) {
+    const uint32_t *b = crc_composed(tab) + kCrcbXl;
+    asm volatile("" : "+s"(b));
+    return b[l];
+}
+// xl[l] the same way, for what follows the row loop
+__device__ __forceinline__ uint32_t crc_xl(const DevTables &tab, uint32_t l) {
+    const uint32_t *x = tab.crcx;
+    asm volatile("" : "+s"(x));
+    return x[l];
+}
+template <uint32_t CB>
+__device__ __forceinline__ uint32_t crc_piece_b(const char *lds, uint32_t B, uint32_t p0, uint32_t L) {
+    const uint32_t q = p0 ^ B;
+    return __builtin_amdgcn_bitop3_b32(
+        __builtin_amdgcn_bitop3_b32(CRC_T(0, q, 0), CRC_T(1, q, 1), CRC_T(2, q, 2), 0x96), CRC_T(3, q, 3), L, 0x96);
+}
+// shift(A, 1008 B): what crc_piece (S = 16) does first
+template <uint32_t CB>
+__device__ __forceinline__ uint32_t crc_shift1008(const char *lds, uint32_t A) {
+    return __builtin_amdgcn_bitop3_b32(CRC_T(16, A, 0), CRC_T(17, A, 1), CRC_T(18, A, 2), 0x96) ^ CRC_T(19, A, 3);
 }
 
 // byte-serial tail: crc_raw(shift(A,1008), first n bytes of the piece)

@@ -12,8 +12,9 @@
 //     round-1 constants of the counter blocks.
 //   * gcm_main: one 1024-thread workgroup per task (block, <=4 MiB range).
 //     LDS holds a 32-way replicated T0|T2 AES table (64 KiB, conflict-free),
-//     the 16 x 256 GHASH table for "multiply by H^64" (64 KiB) and the
-//     slice-by-16 CRC32C tables (20 KiB).  Each wave owns whole 32 KiB
+//     the 16 x 256 GHASH table for "multiply by H^64" (64 KiB), the
+//     slice-by-16 CRC32C tables (20 KiB, + 4 KiB composed with the row shift)
+//     and the task's rounds-1-2 table (4 KiB).  Each wave owns whole 32 KiB
 //     segments; a wave row is 64 lanes x 16 B = 1 KiB.  Per row a lane:
 //     AES-CTR of its counter, XOR, store, GHASH Horner step acc = acc*H^64 ^ C,
 //     CRC32C step over the plaintext.  At segment end the lane CRCs are
@@ -38,25 +39,31 @@
 namespace jfsx {
 
 // ---------------------------------------------------------------------------
-// LDS map of gcm_main (bytes): [0, 20K) CRC tables, [20K, 84K) GHASH table,
-// [84K, 148K) AES T0|T2, [148K, +2K) GHASH basis staging.  Every table's base
+// LDS map of gcm_main (bytes): [0, 20K) CRC tables, [20K, 24K) the composed
+// CRC tables TT_0..3 (B form, jfsx_dev.h), [24K, 88K) GHASH table, [88K, 152K)
+// AES T0|T2, [152K, +2K) GHASH basis staging, +1K segment shares, then the
+// task's rounds-1-2 table P (4 KiB, aes_ctr_blocks_u).  Every table's base
 // is reached through the 16-bit ds_read offset: the CRC and GHASH bases
 // directly, the AES base as 0x10000 (bit 16 of the lane's v_perm operand loff)
-// plus the offset 20K.  So no lookup spends a VALU op on its base.
+// plus the offset 24K.  So no table lookup spends a VALU op on its base; P,
+// above 128 KiB, is read once per row and pays one add for its base.
 // ---------------------------------------------------------------------------
 // plaintext in and ciphertext out as non-temporal block streams (coalesced
 // 1 KiB rows, read or written once): +0.7 % same box (profiles/r4/ab_gcm_rows.txt)
 constexpr int kAeadNt = 3;
 constexpr uint32_t kLdsCrc = 0;
-constexpr uint32_t kLdsGh = 20480;              // GHASH T[b][j]: kLdsGh + (b << 8) | (j << 4)
-constexpr uint32_t kLdsAesOff = 20480;          // ds_read offset of the AES table
+constexpr uint32_t kLdsTT = 20480;              // TT_0..3: kLdsTT + (k << 10) | (byte << 2)
+constexpr uint32_t kLdsGh = 24576;              // GHASH T[b][j]: kLdsGh + (b << 8) | (j << 4)
+constexpr uint32_t kLdsAesOff = 24576;          // ds_read offset of the AES table
 constexpr uint32_t kLdsAes = 65536 + kLdsAesOff;  // AES [idx][T0 x32 | T2 x32]: 0x10000 | (idx << 8) | (r << 2), + offset
 constexpr uint32_t kLdsBasis = kLdsAes + 65536;
 // row-split tasks: per segment of the task, the XOR of the waves' raw CRC
 // shares (128 segments of 32 KiB per 4 MiB task) and a flag per segment
 constexpr uint32_t kLdsSegRaw = kLdsBasis + 2048;
 constexpr uint32_t kLdsSegFlag = kLdsSegRaw + 512;
-constexpr uint32_t kLdsBytes = kLdsSegFlag + 512;
+// P[c], c = the counter's low byte: round 2's four lookups on column 0, 16 B
+constexpr uint32_t kLdsP = kLdsSegFlag + 512;
+constexpr uint32_t kLdsBytes = kLdsP + 4096;
 
 __device__ __forceinline__ uint32_t rotl8(uint32_t x) { return __builtin_amdgcn_alignbit(x, x, 24); }
 __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
@@ -149,8 +156,19 @@ __device__ __forceinline__ void aes_r2_uniform(const char *lds, uint32_t loff, c
     u[3] = xor3(TA(a3, 0), TB(a1, 2), rotl8(TB(a2, 3) ^ rk[11]));
 }
 
+// What is left of rounds 1-2 varies with the counter's low byte c and the key
+// alone: a0 = k1[0] ^ rotl8(T2[c ^ byte 3 of rk[3]]) and round 2's four
+// lookups on a0.  aes_r2_entry gives them for one c; gcm_task builds the
+// task's table P[256] of them, and a row reads its entry with one ds_read_b128
+// (the 64 lanes of a row have consecutive counters: conflict-free).
+__device__ __forceinline__ uint4 aes_r2_entry(const char *lds, uint32_t loff, uint32_t rk3, uint32_t k10, uint32_t c) {
+    const uint32_t x3 = (c << 24) ^ rk3;
+    const uint32_t a0 = k10 ^ rotl8(TB(x3, 3));
+    return make_uint4(TA(a0, 0), rotl8(TB(a0, 3)), TB(a0, 2), rotl8(TA(a0, 1)));
+}
+
 // Keystream blocks of NS rows (the chains interleave for ILP) with rounds 1-2
-// taken from the lane's counter-uniform terms u;
+// taken from the task's table P and the lane's counter-uniform terms u;
 // ks comes out without the last round key (rk[56..59]).
 // side(AesStep<i>) runs after the i-th of the 12 round groups (rounds 1-2, then
 // 3 .. 13): the caller's place for work that fills the rounds' latency (the
@@ -174,12 +192,11 @@ __device__ __forceinline__ void aes_ctr_blocks_u(const char *lds, uint32_t loff,
 #define UC(t, w) (__builtin_amdgcn_bitop3_b32((t), cym[s], du[s][w], 0x78) ^ u[s][w]) /* t ^ (cym & du) ^ u */
 #pragma unroll
     for (int s = 0; s < NS; s++) {
-        const uint32_t x3 = __builtin_bswap32(ctr[s]) ^ rk[3];
-        const uint32_t a0 = k1[0] ^ rotl8(TB(x3, 3));
-        b[s][0] = UC(TA(a0, 0), 0);
-        b[s][1] = UC(rotl8(TB(a0, 3)), 1);
-        b[s][2] = UC(TB(a0, 2), 2);
-        b[s][3] = UC(rotl8(TA(a0, 1)), 3);
+        const uint4 pe = lds_u4(lds, ((ctr[s] << 4) & 0xff0u) + kLdsP);
+        b[s][0] = UC(pe.x, 0);
+        b[s][1] = UC(pe.y, 1);
+        b[s][2] = UC(pe.z, 2);
+        b[s][3] = UC(pe.w, 3);
     }
 #undef UC
     side(AesStep<0>());
@@ -477,7 +494,7 @@ __device__ uint64_t g_wgtrace[4 * 65536];
 // and CRC tables are already in LDS; the GHASH table of the task's key is
 // built here.  Every thread of the workgroup calls this.
 // KL1: in the two-row loop, K of the CRC step's data-only slice lookups come
-// from the vector L1 instead of the LDS (crc_piece_l1; 0: all from the LDS).
+// from the vector L1 instead of the LDS (crc_piece_b; 0: all from the LDS).
 // Only where the CRC covers the loaded side, so the gathers can be issued
 // inside the AES rounds, long before the step that needs them.
 template <bool OPEN, int CRCMODE, bool BS, int KL1>
@@ -493,6 +510,16 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
     if (tid < 128)
         reinterpret_cast<uint4 *>(lds + kLdsBasis)[tid] = reinterpret_cast<const uint4 *>(sch->basis)[tid];
     if (tid < 256) reinterpret_cast<uint32_t *>(lds + kLdsSegRaw)[tid] = 0u;  // raw shares and flags
+    // the task's rounds-1-2 table; its readers of the task before are behind
+    // the caller's barrier
+    if (wave < 4) {
+        // (made here, per task, from the wave index: hoisted out of the task
+        // loop, c, the entry's address and c << 24 would each hold a register
+        // through the rows)
+        uint32_t c = (wave << 6) | lane;
+        asm volatile("" : "+v"(c));
+        reinterpret_cast<uint4 *>(lds + kLdsP)[c] = aes_r2_entry(lds, loff, sch->rk[3], sch->k1[0], c);
+    }
     __syncthreads();
     {
         uint4 *lg = reinterpret_cast<uint4 *>(lds + kLdsGh);
@@ -618,6 +645,14 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
     // the CRC's input is the loaded row itself: the plaintext in Seal, the
     // ciphertext (JFSX_CRC_CT) in Open
     constexpr bool kL1 = KL1 > 0 && kRowSplit && CRCMODE != 0 && OPEN == ((CRCMODE & 4) != 0);
+    // the L1 path's row loop has no use for xl (its segment ends take xlB):
+    // what follows the loop loads it where it is used, so it holds no
+    // register through the rows
+    auto xl_here = [&]() { return kL1 ? crc_xl(tab, lane) : xl; };
+    static_assert(!kL1 || KL1 == 12, "B form: TT_4..15 are in the L1 image only");
+    // wave-uniform: st.A is in B form (crc_piece_b), as the two-row loop leaves
+    // it; whatever follows the loop takes it back to A form
+    bool bform = false;
     if (act && rf >= r0 + UR) {
         uint4 nn[UR];
 #pragma unroll
@@ -631,7 +666,8 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
         // pairs), so the compiler drops the segment-end test of the first row
         // of a pair, which cannot end a segment
         const uint32_t rb0 = (uint32_t)((ld0 - c0) >> 10) / 2u * 2u;
-        const CrcL1Base l1g = kL1 ? crc_l1_base(tab.crc) : CrcL1Base{0, 0};
+        // (the gathers read TT_4..15: the loop keeps the CRC state in B form)
+        const CrcL1Base l1g = kL1 ? crc_l1_base(crc_composed(tab)) : CrcL1Base{0, 0};
         for (; r0 + UR - 1 < rf; r0 += UR) {
             uint4 dd[UR];
 #pragma unroll
@@ -720,17 +756,20 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
                 const uint4 cq = crc_src<CRCMODE>(c, p);
                 ghash_step(lds, st.acc, gl, c);
                 if constexpr (kL1)
-                    st.A = crc_piece_l1<kLdsCrc, (kL1 ? KL1 : 4)>(lds, st.A, cq.x, cq.y, cq.z, cq.w, crcL[u]);
+                    st.A = crc_piece_b<kLdsTT>(lds, st.A, cq.x, crcL[u]);
                 else if (CRCMODE)
                     st.A = crc_piece<kLdsCrc>(lds, st.A, cq.x, cq.y, cq.z, cq.w);
                 if (CRCMODE && ((rb0 + (uint32_t)r0 + u) & 31) == 31) {
-                    crc_segment_done<CRCMODE>(blk, tab, lane, xl, st.seg0, st.A, st.seg0 < st.sub0, lds, c0);
+                    crc_segment_done<CRCMODE>(blk, tab, lane, kL1 ? crc_xlb(tab, lane) : xl, st.seg0,
+                                              st.A, st.seg0 < st.sub0, lds, c0);
                     st.A = 0;
                     st.seg0 += kSeg;
                 }
             }
         }
         if (r0 < rf) nxt = ald16<kAeadNt>(src + ld0 + 1024 * r0 + lo);
+        // the loop ran, and its last row did not end a segment (A = 0 there)
+        if constexpr (kL1) bform = ((rb0 + (uint32_t)r0) & 31) != 0;
     }
     // The rows left over, one at a time.  From here to the end of the stream
     // epilogue the steps keep the form of loops over the wave's streams, of
@@ -759,11 +798,17 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
             ast16<kAeadNt>(dst + o, OPEN ? p : c);
             const uint4 cq = crc_src<CRCMODE>(c, p);
             ghash_step(lds, st.acc, gl, c);
-            if (CRCMODE) st.A = crc_piece<kLdsCrc>(lds, st.A, cq.x, cq.y, cq.z, cq.w);
+            if constexpr (kL1) {
+                // a B-form state is already shifted: the no-shift entry
+                const uint32_t sh = bform ? st.A : crc_shift1008<kLdsCrc>(lds, st.A);
+                st.A = crc_piece<kLdsCrc, -1>(lds, sh, cq.x, cq.y, cq.z, cq.w);
+            } else if (CRCMODE)
+                st.A = crc_piece<kLdsCrc>(lds, st.A, cq.x, cq.y, cq.z, cq.w);
         }
+        if constexpr (kL1) bform = false;
         if (CRCMODE && ((uint32_t)((ld0 - c0) >> 10) + (uint32_t)r & 31) == 31) {
             if (act) {
-                crc_segment_done<CRCMODE>(blk, tab, lane, xl, st.seg0, st.A, st.seg0 < st.sub0, lds, c0);
+                crc_segment_done<CRCMODE>(blk, tab, lane, xl_here(), st.seg0, st.A, st.seg0 < st.sub0, lds, c0);
                 st.A = 0;
                 st.seg0 += kSeg;
             }
@@ -778,14 +823,29 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
         // lanes whose last piece lies in the last full row: their CRC shift to
         // a segment end starts at that row's end (lend == 0, crc_segment_end)
         const uint64_t tailRef = st.sub0 + 1024 * rf;
+        // a stream that ends in B form: every lane's last piece lies in the
+        // last full row (lend == 0), so xlB in xl's place finishes it.  Ahead
+        // of a ragged tail, whose rows and segment ends take A form, the
+        // state is multiplied back by x^-8064 (xlB[63]) instead.
+        if constexpr (kL1) {
+            if (bform && tailRef < st.sub1) {
+                st.A = crc_mulmod(crc_xlb(tab, 63), st.A);
+                bform = false;
+            }
+        }
         // ragged remainder of this stream (block tail)
         for (uint64_t row = tailRef; row < st.sub1; row += 1024)
-            st = row_generic<OPEN, CRCMODE>(lds, loff, gl, sch, blk, tab, lane, xl, st, row, c0, c1);
+            st = row_generic<OPEN, CRCMODE>(lds, loff, gl, sch, blk, tab, lane, xl_here(), st, row, c0, c1);
         // a stream that ended inside a segment still owes that segment's CRC
         // (or, when another wave holds the rest of the segment, its share)
         if (CRCMODE && act && st.seg0 < st.sub1) {
             const uint64_t seg1 = st.seg0 + kSeg < c1 ? st.seg0 + kSeg : c1;
-            crc_segment_end<CRCMODE>(blk, tab, lane, xl, st.seg0, seg1, st.A, st.lend, tailRef,
+            uint32_t xle;
+            if constexpr (kL1)
+                xle = bform ? crc_xlb(tab, lane) : crc_xl(tab, lane);
+            else
+                xle = xl;
+            crc_segment_end<CRCMODE>(blk, tab, lane, xle, st.seg0, seg1, st.A, st.lend, tailRef,
                                      st.seg0 < st.sub0 || st.sub1 < seg1, lds, (uint32_t)((st.seg0 - c0) / kSeg));
             st.seg0 = st.sub1;
         }
@@ -894,6 +954,10 @@ __global__ __launch_bounds__(GcmShape<BS>::threads) void gcm_main_k(const Task *
             uint4 *lc = reinterpret_cast<uint4 *>(lds + kLdsCrc);
             for (uint32_t i = tid; i < 1280; i += GcmShape<BS>::threads) lc[i] = gc[i];
         }
+        if (KL1) {
+            const uint4 *gt = reinterpret_cast<const uint4 *>(crc_composed(tab));
+            if (tid < 256) reinterpret_cast<uint4 *>(lds + kLdsTT)[tid] = gt[tid];
+        }
     }
 #ifdef JFSX_KS_PHASES
     __syncthreads();
@@ -906,7 +970,7 @@ __global__ __launch_bounds__(GcmShape<BS>::threads) void gcm_main_k(const Task *
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;  // wave index in an SGPR
     const uint32_t loff = ((lane & 31) << 2) | 0x00010000u;  // AES replica offset | table base
     const GhLane gl = gh_lane(lane);
-    const uint32_t xl = CRCMODE ? tab.crcx[lane] : 0u;
+    const uint32_t xl = CRCMODE && !KL1 ? tab.crcx[lane] : 0u;  // (KL1: gcm_task loads it where it is used)
     if (tid == 0) s_task = atomicAdd(queue, 1u);
     for (;;) {
         // also orders this task's table writes after the previous task's readers

@@ -31,7 +31,8 @@ constexpr int kThreads = kWaves * 64;
 #define JFSX_GH8 1
 #endif
 // Fused CRC in the 16-wave GCM kernel: K of the step's 12 data-only slice
-// lookups through the vector L1 (4, 8 or 12; crc_piece_l1, jfsx_dev.h), issued
+// lookups through the vector L1 (12 since the composed tables of round 9:
+// TT_4..15 exist in the L1 image alone; crc_piece_b, jfsx_dev.h), issued
 // inside the AES rounds in groups of LG and folded LAG round groups later
 // (gcm_task; DESIGN 4.1, round 7, has the measurements behind 12 / 4 / 3), and
 // whether a context takes that path unless told otherwise (crc_l1_choice).
@@ -252,8 +253,10 @@ namespace jfsx {
 struct DevTables {
     const uint32_t *aes;    // 16384 dwords: T0|T2 replicated x32 per index
     const uint32_t *crc;    // 32 x 256 dwords: U0..U15 (slice-by-16), shift 1008 B, 4032 B, 1024 B, 4096 B
-    const uint32_t *crcx;   // 64 lane shift constants, 32 x8pow, K_full
+    const uint32_t *crcx;   // 64 lane shift constants, 32 x8pow, K_full (kCrcxDwords), then the composed tables:
+                            // 16 x 256 dwords TT0..15 = x^8064 * U0..15 and 64 lane constants xlB (B form, jfsx_dev.h)
 };
+constexpr uint32_t kCrcxDwords = 192;  // crcx proper; the composed tables follow it in the device image
 void launch_gcm_keysetup(hipStream_t s, int n, const KeyIn *keys, const BlkDev *blks, GcmSched *sched,
                          DevTables t, bool bitslice);
 // persistent over min(ntasks, ncu) workgroups; queue: 4 device bytes the caller zeroed (enqueue_aead uploads it)

@@ -294,6 +294,20 @@ def debug_tables():
     return aes, crc, crcx
 
 
+def debug_crc_composed():
+    """The composed CRC tables of the GCM kernel's two-row loop (host built,
+    no device; jfsx_debug_crc_composed is a test hook outside the ABI):
+    (TT, xlB), TT[k * 256 + v] = x^8064 * U_k[v] for k < 16 and the 64 lane
+    constants xlB[l] = xl[l] * x^-8064."""
+    fn = load_library().jfsx_debug_crc_composed
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    tt = np.empty(4096, np.uint32)
+    xlb = np.empty(64, np.uint32)
+    fn(tt.ctypes.data, xlb.ctypes.data)
+    return tt, xlb
+
+
 PLAN_GCM, PLAN_CHACHA, PLAN_CRC = 0, 1, 2
 
 
