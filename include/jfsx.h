@@ -24,12 +24,17 @@
  *   jfsx_store_batch     uploadStagingFile's verified re-read +     pkg/chunk/cached_store.go:944-999, :371-413
  *                        upload's Compress + Encrypt + checksums,   (disk_cache.go:433-483, checksum.go:31-53)
  *                        one call
+ *   jfsx_rsa_oaep_decrypt_batch  rsaEncryptor.Decrypt, per read window  pkg/object/encrypt.go:132-134 (called :207-210)
+ *   jfsx_rsa_oaep_encrypt_batch  rsaEncryptor.Encrypt, per upload window pkg/object/encrypt.go:128-130 (called :169)
  *   JFSX_AES256GCM /     NewDataEncryptor algo "aes256gcm-rsa" /    pkg/object/encrypt.go:142-162
  *   JFSX_CHACHA20P1305   "chacha20-rsa"
  *
- * RSA-OAEP key wrapping (encrypt.go:124-134) stays with the caller: the
- * engine takes the 32-byte data key and 12-byte nonce per block as inputs
- * (the reference draws both from crypto/rand, encrypt.go:165-180).
+ * RSA-OAEP key wrapping (encrypt.go:124-134) is a batch call of its own on
+ * either side (jfsx_rsa_oaep_encrypt_batch / _decrypt_batch); the AEAD entry
+ * points take the already-wrapped key bytes.  Randomness stays with the
+ * caller: the engine takes the 32-byte data key, the 12-byte nonce and the
+ * 32-byte OAEP seed per block as inputs (the reference draws all three from
+ * crypto/rand, encrypt.go:165-180 and rsa.EncryptOAEP) and draws none itself.
  *
  * Threading: a context may be used from several host threads; calls on one
  * context are serialised internally (one HIP stream per context).  Use one
@@ -446,6 +451,22 @@ int jfsx_rsa_key_new(jfsx_ctx *ctx, const uint8_t *p, const uint8_t *q, const ui
 int jfsx_rsa_key_free(jfsx_rsa_key *key);
 int jfsx_rsa_oaep_decrypt_batch(jfsx_ctx *ctx, const jfsx_rsa_key *key, int n, const uint8_t *ct, uint64_t ct_stride,
                                 const uint32_t *ct_len, uint8_t *msg, uint64_t msg_stride, int32_t *msg_len);
+/* Batched RSA-OAEP key wrap, the write side of the unwrap: replaces, per
+ * object, rsaEncryptor.Encrypt = rsa.EncryptOAEP(sha256, rand, &priv.PublicKey,
+ * key, label) (pkg/object/encrypt.go:128-130, called at :169) for every object
+ * of an upload window at once, on the GPU.  key: as above (its n = p q and its
+ * label); e: the public exponent, 2 <= e <= 2^31 - 1 as Go's checkPub takes it.
+ * All pointers are host memory.  Item i reads msg_len[i] bytes at msg +
+ * i*msg_stride and its 32-byte OAEP seed at seed + 32*i: the seeds are the
+ * caller's randomness (Go reads them from rand), the engine draws none.  It
+ * writes exactly 256 bytes at ct + i*ct_stride.  status[i] = 0, or -1 for Go's
+ * "message too long for RSA key size" (msg_len[i] > 190; the 256 bytes are then
+ * zero, the other items unaffected).  JFSX_EINVAL, before anything runs: null
+ * seed, ct or status, ct_stride < 256, msg_len[i] > msg_stride, e out of range,
+ * n < 0.  n == 0 returns 0. */
+int jfsx_rsa_oaep_encrypt_batch(jfsx_ctx *ctx, const jfsx_rsa_key *key, uint32_t e, int n, const uint8_t *msg,
+                                uint64_t msg_stride, const uint32_t *msg_len, const uint8_t *seed /* n x 32 bytes */,
+                                uint8_t *ct, uint64_t ct_stride, int32_t *status);
 
 /* object-store checksum of header || C || tag (checksum.go:31-53) from the
  * big-endian 32 KiB segment CRCs of C that a GEN|CT batch returned */

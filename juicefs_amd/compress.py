@@ -370,7 +370,9 @@ def upload_blocks_fused(store, keys, blocks, compressor, enc=None, checksums=Tru
 
     Key and nonce of block i are drawn from enc's rand in DataEncryptor.Encrypt's
     order (key, then the wrap on the host by keyEncryptor.Encrypt, then the
-    nonce; encrypt.go:165-180), block by block.
+    nonce; encrypt.go:165-180), block by block; with DataEncryptor(wrap="gpu")
+    the keys of all blocks are wrapped in one engine call first, each block's
+    OAEP seed drawn between its key and its nonce (DataEncryptor.draw_keys).
     Returns (objects, crcs) with crcs[i] == checksum(blocks[i]), or the objects
     alone with checksums=False."""
     if not isinstance(compressor, (LZ4, ZStandard)):
@@ -385,10 +387,7 @@ def upload_blocks_fused(store, keys, blocks, compressor, enc=None, checksums=Tru
         hdrs = [b""] * len(blocks)
     else:
         algo, items = enc.algo, []
-        for b in blocks:
-            key = enc._rand(enc.keyLen)
-            cipherkey = enc.keyEncryptor.Encrypt(key)
-            nonce = enc._rand(12)
+        for b, (key, cipherkey, nonce) in zip(blocks, enc.draw_keys(len(blocks))):
             hdrs.append(bytes([len(cipherkey) >> 8, len(cipherkey) & 0xFF, len(nonce)]) + cipherkey + nonce)
             items.append((key, nonce, b))
     if not blocks:

@@ -3835,4 +3835,48 @@ int jfsx_rsa_oaep_decrypt_batch(jfsx_ctx *c, const jfsx_rsa_key *k, int n, const
     return 0;
 }
 
+// batched RSA-OAEP key wrap (rsaEncryptor.Encrypt, encrypt.go:128-130, called
+// per object at :169), on the unwrap's stream and grow-only workspace
+int jfsx_rsa_oaep_encrypt_batch(jfsx_ctx *c, const jfsx_rsa_key *k, uint32_t e, int n, const uint8_t *msg,
+                                uint64_t msg_stride, const uint32_t *msg_len, const uint8_t *seed, uint8_t *ct,
+                                uint64_t ct_stride, int32_t *status) {
+    constexpr size_t K = jfsx_rsa::kModBytes, S = kRsaWrapSlot, H = jfsx_rsa::kHash;
+    if (!c || !k || n < 0 || e < jfsx_rsa::kMinE || e > jfsx_rsa::kMaxE) return JFSX_EINVAL;  // e: Go's checkPub
+    if (n == 0) return 0;
+    if (!msg_len || !seed || !ct || !status || ct_stride < K) return JFSX_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (msg_len[i] > msg_stride || (msg_len[i] && !msg)) return JFSX_EINVAL;
+    if (k->device != c->device) return JFSX_EINVAL;
+    // device: msg slots | seeds | lengths (one copy in) | EM limbs | ct (one copy out)
+    const size_t o_msg = 0, o_seed = align256(S * n), o_len = o_seed + align256(H * n),
+                 inbytes = o_len + align256(4 * (size_t)n), o_em = inbytes, o_ct = o_em + align256(K * n),
+                 dbytes = o_ct + align256(K * n);
+    const size_t hbytes = std::max(inbytes, K * n);
+    std::lock_guard<std::mutex> g(c->mu);
+    CtxScope es_(c);
+    HIP_OK(hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure_dev(c, &c->rsa_d, &c->rsa_dcap, dbytes))) return rc;
+    if ((rc = ensure_host(&c->rsa_h, &c->rsa_hcap, hbytes))) return rc;
+    char *h = c->rsa_h;
+    memset(h, 0, inbytes);
+    for (int i = 0; i < n; i++) {
+        // Go: "message too long for RSA key size"; the kernels give such an item 256 zero bytes
+        status[i] = msg_len[i] > (uint32_t)jfsx_rsa::kMaxMsg ? -1 : 0;
+        if (status[i] == 0 && msg_len[i]) memcpy(h + o_msg + S * i, msg + msg_stride * i, msg_len[i]);
+        memcpy(h + o_seed + H * i, seed + H * i, H);
+        ((uint32_t *)(h + o_len))[i] = msg_len[i];
+    }
+    char *d = c->rsa_d;
+    HIP_OK(hipMemcpyAsync(d, h, inbytes, hipMemcpyHostToDevice, c->stream));
+    launch_begin();
+    launch_rsa_wrap(c->stream, k->d_key, e, n, (const uint8_t *)(d + o_msg), (const uint32_t *)(d + o_len),
+                    (const uint8_t *)(d + o_seed), (uint32_t *)(d + o_em), (uint8_t *)(d + o_ct));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(h, d + o_ct, K * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < n; i++) memcpy(ct + ct_stride * i, h + K * i, K);
+    return 0;
+}
+
 }  // extern "C"

@@ -363,4 +363,11 @@ void launch_store_verdict(hipStream_t s, int n, const StoreBlk *sb, const BlkOut
 void async_detach(jfsx_ctx *c);  // jfsx_agg.cpp
 void launch_rsa_unwrap(hipStream_t s, const void *key, int n, const uint8_t *ct, uint32_t *mh, uint8_t *em,
                        int32_t *len);
+// batched RSA-OAEP wrap with public exponent e: item i's message in the
+// kRsaWrapSlot-byte slot i of msg (len[i] bytes; above the OAEP capacity: 256
+// zero bytes out), its seed at seed + 32 i; em = n x 64 words of workspace, ct =
+// n x 256 bytes out (all device memory)
+constexpr int kRsaWrapSlot = 192;
+void launch_rsa_wrap(hipStream_t s, const void *key, uint32_t e, int n, const uint8_t *msg, const uint32_t *len,
+                     const uint8_t *seed, uint32_t *em, uint8_t *ct);
 }  // namespace jfsx

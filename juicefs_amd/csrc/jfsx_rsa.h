@@ -10,8 +10,13 @@
 // and MGF1 hash.  Primes are 1024-bit (RSA-2048, the size the reference docs
 // use), in 32 little-endian 32-bit limbs; products use Montgomery CIOS.
 //
+// The write side, rsaEncryptor.Encrypt = rsa.EncryptOAEP (encrypt.go:128-130),
+// is the last part of this file: EME-OAEP encoding and the public operation
+// EM^e mod n, modulo the 2048-bit n itself.
+//
 // Host/device portable: the includer defines JFSX_HD.  Every function is
-// pinned on the CPU by tests/test_rsa.py against libcrypto's RSA-OAEP.
+// pinned on the CPU by tests/test_rsa.py (the unwrap) and tests/test_rsa_wrap.py
+// (the wrap) against libcrypto's RSA-OAEP and a big-integer model.
 //
 // Constant time with respect to the private key and the decrypted message,
 // as Go's rsa.DecryptOAEP is (crypto/internal/bigmod, subtle.ConstantTime*):
@@ -306,7 +311,30 @@ struct Key {
     uint32_t pinv, qinv32;              // -p^-1, -q^-1 mod 2^32
     int32_t dp_bits, dq_bits;           // exponent bit lengths
     uint8_t lhash[32];                  // SHA-256(label)
+    // the key wrap's constants for n in 28-bit limbs (R'' = 2^(28 kN28), below)
+    uint32_t r2n28[2 * kLimbs];         // R''^2 mod n
+    uint32_t ninv28;                    // -n^-1 mod 2^28
 };
+
+// 2^bits mod m for an odd m of nl <= 2 kLimbs limbs (mont_r2 at another width)
+JFSX_HD void mont_r2_wide(const uint32_t *m, int nl, uint32_t *r2, int bits) {
+    uint32_t x[2 * kLimbs + 1];
+    for (int j = 0; j <= nl; j++) x[j] = 0;
+    x[0] = 1;
+    for (int k = 0; k < bits; k++) {  // x = 2^k mod m
+        uint32_t c = 0;
+        for (int j = 0; j <= nl; j++) {
+            const uint32_t nc = x[j] >> 31;
+            x[j] = (x[j] << 1) | c;
+            c = nc;
+        }
+        if (x[nl] || geq(x, m, nl)) {
+            const uint32_t b = sub_in(x, m, nl);
+            x[nl] -= b;
+        }
+    }
+    for (int j = 0; j < nl; j++) r2[j] = x[j];
+}
 
 JFSX_HD int bit_length(const uint32_t *x, int nlimbs) {
     for (int i = nlimbs - 1; i >= 0; i--)
@@ -347,6 +375,8 @@ JFSX_HD bool key_setup(Key &k, const uint8_t *p, const uint8_t *q, const uint8_t
         k.n[i + kLimbs] = (uint32_t)c;
     }
     sha256_2(label, label_len, label, 0, k.lhash);
+    mont_r2_wide(k.n, 2 * kLimbs, k.r2n28, 2 * 28 * 74);  // 74 = kN28
+    k.ninv28 = mont_inv32(k.n[0]) & ((1u << 28) - 1);
     return true;
 }
 
@@ -740,6 +770,331 @@ JFSX_HD int decrypt(const Key &k, const uint8_t *ct, uint8_t em[kModBytes]) {
     crt(k, m1, m2, m);
     to_be(m, 2 * kLimbs, em, kModBytes);
     return oaep_decode(em, kModBytes, k.lhash);
+}
+
+// ---------------------------------------------------------------------------
+// The key wrap, the write side: rsaEncryptor.Encrypt = rsa.EncryptOAEP(
+// sha256.New(), rand, &privKey.PublicKey, key, []byte("keys"))
+// (pkg/object/encrypt.go:128-130, called at :169).  EME-OAEP encoding with a
+// seed the caller draws, then EM^e mod n with the public exponent: no CRT, so
+// the arithmetic is modulo the 2048-bit n itself, in kN28 = 74 limbs of 28
+// bits with R'' = 2^(28 kN28).
+//
+// The lazy column accumulators of mont_mul28 carry over, with a tighter bound:
+// a column takes at most kN28 rows of two products, each at most (2^28 - 1)^2,
+// so at most 148 (2^28 - 1)^2 < 2^63.21, plus one carry below 2^37 when it
+// reaches column 0: it fits an unsigned 64-bit word with under one bit to
+// spare, and only because both operands and the modulus are normalized limbs
+// (<= 2^28 - 1) of values < n.  The products' results are therefore always
+// normalized and < n (one masked final subtract), never "< 2n".
+//
+// e is public (Go's checkPub takes 2 <= e <= 2^31 - 1): its bits steer a
+// plain left-to-right square-and-multiply.  The operands (the encoded data
+// key) steer nothing: no branch and no address depends on them.
+// ---------------------------------------------------------------------------
+constexpr int kNLimbs = 2 * kLimbs;                    // n in 32-bit limbs
+constexpr int kN28 = 74;                               // and in 28-bit limbs (2072 bits)
+constexpr int kMaxMsg = kModBytes - 2 * kHash - 2;     // OAEP capacity: 190 bytes
+constexpr uint32_t kMinE = 2, kMaxE = 0x7FFFFFFFu;     // Go's checkPub
+
+// EME-OAEP encode (RFC 8017 7.1.1 step 2, Go's EncryptOAEP): em = 00 ‖
+// maskedSeed ‖ maskedDB with DB = lhash ‖ PS ‖ 01 ‖ msg; len <= kMaxMsg.  Only
+// the length places bytes; the message and seed bytes are moved and hashed.
+JFSX_HD void oaep_encode(const uint8_t lhash[32], const uint8_t *msg, int len, const uint8_t *seed,
+                         uint8_t em[kModBytes]) {
+    uint8_t *ms = em + 1, *db = em + 1 + kHash;
+    const int dblen = kModBytes - kHash - 1, sep = dblen - 1 - len;
+    em[0] = 0;
+    for (int i = 0; i < kHash; i++) db[i] = lhash[i], ms[i] = seed[i];
+    for (int i = kHash; i < dblen; i++) db[i] = i < sep ? 0 : i == sep ? 1 : msg[i - sep - 1];
+    mgf1_xor(ms, kHash, db, dblen);
+    mgf1_xor(db, dblen, ms, kHash);
+}
+
+// 28-bit limb j of a value in nl32 32-bit limbs (zero past its end)
+JFSX_HD uint32_t limb28(const uint32_t *x, int nl32, int j) {
+    const int bit = 28 * j, l = bit >> 5, o = bit & 31;
+    uint64_t v = l < nl32 ? x[l] : 0u;
+    if (l + 1 < nl32) v |= (uint64_t)x[l + 1] << 32;
+    return (uint32_t)(v >> o) & kM28;
+}
+// n28 28-bit limbs -> n32 32-bit limbs (from28 at another width)
+JFSX_HD void from28_wide(const uint32_t *y, int n28, uint32_t *x, int n32) {
+#pragma unroll
+    for (int j = 0; j < n32; j++) {
+        const int bit = 32 * j, l = bit / 28, o = bit % 28;
+        uint64_t v = l < n28 ? (uint64_t)y[l] >> o : 0u;
+        if (l + 1 < n28) v |= (uint64_t)y[l + 1] << (28 - o);
+        x[j] = (uint32_t)v;
+    }
+}
+
+// out = a b R''^-1 mod m for a 2048-bit odd m: a, b < m in kN28 normalized
+// limbs, minv = -m^-1 mod 2^28; out normalized and < m.  mont_mul28 at twice
+// the width; the accumulator bound is the one stated above.
+JFSX_HD void mont_mul28_wide(const uint32_t *a, const uint32_t *b, const uint32_t *m, uint32_t minv, uint32_t *out) {
+    JFSX_RSA_TRACE('M', 3);
+    uint64_t acc[kN28];
+#pragma unroll
+    for (int j = 0; j < kN28; j++) acc[j] = 0;
+#pragma unroll
+    for (int i = 0; i < kN28; i++) {
+        const uint32_t ai = a[i];
+#pragma unroll
+        for (int j = 0; j < kN28; j++) acc[j] += (uint64_t)ai * b[j];
+        const uint32_t mi = ((uint32_t)acc[0] * minv) & kM28;
+#pragma unroll
+        for (int j = 0; j < kN28; j++) acc[j] += (uint64_t)mi * m[j];
+        const uint64_t c = acc[0] >> 28;
+#pragma unroll
+        for (int j = 0; j < kN28 - 1; j++) acc[j] = acc[j + 1];
+        acc[kN28 - 1] = 0;
+        acc[0] += c;
+    }
+    // the value is < m (1 + m / R'') < 2m: normalize, then subtract m unless t < m
+    uint32_t t[kN28], d[kN28];
+    uint64_t c = 0;
+#pragma unroll
+    for (int j = 0; j < kN28; j++) {
+        c += acc[j];
+        t[j] = (uint32_t)c & kM28;
+        c >>= 28;
+    }
+    uint32_t br = 0;
+#pragma unroll
+    for (int j = 0; j < kN28; j++) {
+        const uint32_t x = t[j] - m[j] - br;
+        d[j] = x & kM28;
+        br = x >> 31;
+    }
+    const uint32_t keep = 0u - br;  // t < m
+#pragma unroll
+    for (int j = 0; j < kN28; j++) out[j] = (t[j] & keep) | (d[j] & ~keep);
+}
+
+// The public exponentiation's schedule, shared by both forms below: one
+// product to enter the Montgomery domain, then for every bit of e under the
+// top one a squaring and, where the bit is set, a multiply by x R''; one
+// product to leave: bit_length(e) + popcount(e) products.  One multiply site
+// in a loop (one copy of the unrolled product in the instruction cache).
+struct PubSchedule {
+    enum Phase { kEnter, kSquare, kMultiply, kLeave };
+    uint32_t e;
+    int bit;    // the bit of e being worked on
+    int phase;  // the product about to run
+};
+JFSX_HD PubSchedule pub_begin(uint32_t e) { return PubSchedule{e, 31 - __builtin_clz(e), PubSchedule::kEnter}; }
+// moves to the step after the current one; false once kLeave has run
+JFSX_HD bool pub_next(PubSchedule &s) {
+    if (s.phase == PubSchedule::kLeave) return false;
+    if (s.phase == PubSchedule::kSquare && ((s.e >> s.bit) & 1u)) {
+        s.phase = PubSchedule::kMultiply;
+    } else {
+        s.bit--;
+        s.phase = s.bit >= 0 ? PubSchedule::kSquare : PubSchedule::kLeave;
+    }
+    return true;
+}
+
+// x^e mod m (x < m, m odd, 2048 bits; 32-bit limbs in and out), kMinE <= e
+JFSX_HD void mod_exp28_pub(const uint32_t *x32, uint32_t e, const uint32_t *m32, uint32_t minv, const uint32_t *r2_32,
+                           uint32_t *out32) {
+    uint32_t m[kN28], xr[kN28], acc[kN28], b[kN28];
+    for (int j = 0; j < kN28; j++) {
+        m[j] = limb28(m32, kNLimbs, j);
+        acc[j] = limb28(x32, kNLimbs, j);
+        b[j] = limb28(r2_32, kNLimbs, j);
+        xr[j] = 0;
+    }
+    PubSchedule s = pub_begin(e);
+#pragma unroll 1
+    do {
+        if (s.phase == PubSchedule::kSquare) {
+            for (int j = 0; j < kN28; j++) b[j] = acc[j];
+        } else if (s.phase == PubSchedule::kMultiply) {
+            for (int j = 0; j < kN28; j++) b[j] = xr[j];
+        } else if (s.phase == PubSchedule::kLeave) {
+            for (int j = 0; j < kN28; j++) b[j] = j == 0;
+        }
+        mont_mul28_wide(acc, b, m, minv, acc);
+        if (s.phase == PubSchedule::kEnter)
+            for (int j = 0; j < kN28; j++) xr[j] = acc[j];
+    } while (pub_next(s));
+    from28_wide(acc, kN28, out32, kNLimbs);
+}
+
+// ---------------------------------------------------------------------------
+// The same on a QUAD of lanes (the GPU kernel's form): the four lanes of one
+// DPP quad share one exponentiation, lane L holding columns kQC L .. kQC L +
+// 18 (4 kQC = 76 >= kN28; columns 74 and 75 stay zero).  Per row of the
+// product the lanes exchange a_i (a broadcast from the lane holding it), the
+// reduction multiplier m_i (a broadcast of lane 0's), and the 64-bit column
+// that moves into the lane below when the accumulator shifts down.  The
+// carries of the normalization ripple through lanes 1, 2, 3 in turn; the
+// final subtract's borrow crosses the lanes as one (generate, propagate) pair
+// per lane.  There is no window table: the live state is acc, x R'', m, the
+// operand and the 19 column accumulators.
+//
+// X is the exchange inside the quad: X::lane (0..3), X::from<K>(v) (lane K's
+// v, in all lanes), X::next(v) / X::prev(v) (v of the lane above / below,
+// cyclically), X::tracing().  The GPU kernel passes DPP quad_perm moves; the
+// CPU pin (tests/harness/rsa_wrap_host.cpp) runs four threads and a barrier.
+// ---------------------------------------------------------------------------
+constexpr int kQC = (kN28 + 3) / 4;  // columns per lane
+
+template <class X>
+JFSX_HD uint64_t next64(const X &x, uint64_t v) {
+    return (uint64_t)x.next((uint32_t)v) | (uint64_t)x.next((uint32_t)(v >> 32)) << 32;
+}
+template <class X>
+JFSX_HD uint64_t prev64(const X &x, uint64_t v) {
+    return (uint64_t)x.prev((uint32_t)v) | (uint64_t)x.prev((uint32_t)(v >> 32)) << 32;
+}
+
+// out = a b R''^-1 mod m on the quad: a, b, m, out are this lane's kQC limbs
+// (normalized, a, b < m); the accumulator bound is mont_mul28_wide's
+template <class X>
+JFSX_HD void mont_mul28_quad(const X &x, const uint32_t *a, const uint32_t *b, const uint32_t *m, uint32_t minv,
+                             uint32_t *out) {
+    if (x.tracing()) JFSX_RSA_TRACE('M', 4);
+    const uint64_t first = (uint64_t)0 - (uint64_t)(x.lane == 0u), inner = (uint64_t)0 - (uint64_t)(x.lane != 3u);
+    uint64_t acc[kQC];
+#pragma unroll
+    for (int j = 0; j < kQC; j++) acc[j] = 0;
+    // one row: + a_i b, + m_i m (m_i from lane 0's column 0), then the columns
+    // move down one: column 0 leaves (its carry joins column 1) and every
+    // lane's first column becomes the last of the lane below
+    auto row = [&](uint32_t ai) {
+#pragma unroll
+        for (int j = 0; j < kQC; j++) acc[j] += (uint64_t)ai * b[j];
+        const uint32_t mi = x.template from<0>(((uint32_t)acc[0] * minv) & kM28);
+#pragma unroll
+        for (int j = 0; j < kQC; j++) acc[j] += (uint64_t)mi * m[j];
+        const uint64_t c = acc[0] >> 28, s = next64(x, acc[0]);
+#pragma unroll
+        for (int j = 0; j < kQC - 1; j++) acc[j] = acc[j + 1];
+        acc[kQC - 1] = s & inner;
+        acc[0] += c & first;
+    };
+#pragma unroll
+    for (int r = 0; r < kQC; r++) row(x.template from<0>(a[r]));
+#pragma unroll
+    for (int r = 0; r < kQC; r++) row(x.template from<1>(a[r]));
+#pragma unroll
+    for (int r = 0; r < kQC; r++) row(x.template from<2>(a[r]));
+#pragma unroll
+    for (int r = 0; r < kN28 - 3 * kQC; r++) row(x.template from<3>(a[r]));
+    // normalize: each lane on its own, then the carry out of lane k - 1
+    // (below 2^37) through lane k, for k = 1, 2, 3
+    uint32_t t[kQC], d[kQC];
+    uint64_t c = 0;
+#pragma unroll
+    for (int j = 0; j < kQC; j++) {
+        c += acc[j];
+        t[j] = (uint32_t)c & kM28;
+        c >>= 28;
+    }
+#pragma unroll
+    for (uint32_t k = 1; k < 4; k++) {
+        uint64_t ci = prev64(x, c) & ((uint64_t)0 - (uint64_t)(x.lane == k));
+#pragma unroll
+        for (int j = 0; j < kQC; j++) {
+            ci += t[j];
+            t[j] = (uint32_t)ci & kM28;
+            ci >>= 28;
+        }
+        c += ci;
+    }
+    // t - m: every lane's borrow out for a borrow in of 0 (g) and of 1 (p),
+    // then the chain over the four (g, p) pairs, the same in all lanes
+    uint32_t g = 0, p = 1;
+#pragma unroll
+    for (int j = 0; j < kQC; j++) {
+        g = (t[j] - m[j] - g) >> 31;
+        p = (t[j] - m[j] - p) >> 31;
+    }
+    uint32_t br = 0, bin = 0;
+    br = x.template from<0>(g) | (x.template from<0>(p) & br);
+    bin |= br & (0u - (uint32_t)(x.lane == 1u));
+    br = x.template from<1>(g) | (x.template from<1>(p) & br);
+    bin |= br & (0u - (uint32_t)(x.lane == 2u));
+    br = x.template from<2>(g) | (x.template from<2>(p) & br);
+    bin |= br & (0u - (uint32_t)(x.lane == 3u));
+    br = x.template from<3>(g) | (x.template from<3>(p) & br);
+#pragma unroll
+    for (int j = 0; j < kQC; j++) {
+        const uint32_t v = t[j] - m[j] - bin;
+        d[j] = v & kM28;
+        bin = v >> 31;
+    }
+    const uint32_t keep = 0u - br;  // t < m
+#pragma unroll
+    for (int j = 0; j < kQC; j++) out[j] = (t[j] & keep) | (d[j] & ~keep);
+}
+
+// x^e mod m on the quad (x < m; 32-bit limbs in, out32 in all four lanes):
+// mod_exp28_pub's schedule
+template <class X>
+JFSX_HD void mod_exp28_pub_quad(const X &x, const uint32_t *x32, uint32_t e, const uint32_t *m32, uint32_t minv,
+                                const uint32_t *r2_32, uint32_t *out32) {
+    uint32_t m[kQC], xr[kQC], acc[kQC], b[kQC];
+    const uint32_t one0 = x.lane == 0u;  // the Montgomery 1's low limb sits in lane 0
+#pragma unroll
+    for (int j = 0; j < kQC; j++) {
+        const int col = kQC * (int)x.lane + j;  // limb28 gives zero for columns 74, 75
+        m[j] = limb28(m32, kNLimbs, col);
+        acc[j] = limb28(x32, kNLimbs, col);
+        b[j] = limb28(r2_32, kNLimbs, col);
+        xr[j] = 0;
+    }
+    PubSchedule s = pub_begin(e);
+#pragma unroll 1
+    do {
+        if (s.phase == PubSchedule::kSquare) {
+#pragma unroll
+            for (int j = 0; j < kQC; j++) b[j] = acc[j];
+        } else if (s.phase == PubSchedule::kMultiply) {
+#pragma unroll
+            for (int j = 0; j < kQC; j++) b[j] = xr[j];
+        } else if (s.phase == PubSchedule::kLeave) {
+#pragma unroll
+            for (int j = 0; j < kQC; j++) b[j] = j == 0 ? one0 : 0u;
+        }
+        mont_mul28_quad(x, acc, b, m, minv, acc);
+        if (s.phase == PubSchedule::kEnter) {
+#pragma unroll
+            for (int j = 0; j < kQC; j++) xr[j] = acc[j];
+        }
+    } while (pub_next(s));
+    // all four quarters of the result in every lane, back to 32-bit limbs
+    uint32_t f[4 * kQC];
+#pragma unroll
+    for (int j = 0; j < kQC; j++) {
+        f[j] = x.template from<0>(acc[j]);
+        f[kQC + j] = x.template from<1>(acc[j]);
+        f[2 * kQC + j] = x.template from<2>(acc[j]);
+        f[3 * kQC + j] = x.template from<3>(acc[j]);
+    }
+    from28_wide(f, kN28, out32, kNLimbs);
+}
+
+// One whole wrap on one thread (the CPU pin; the GPU splits it into an encode
+// kernel and the quad exponentiation): ct = EM^e mod n, kModBytes big-endian
+// bytes, left-padded with zeros.  Returns 0, or -1 for Go's "message too long
+// for RSA key size" (ct all zero).  EM's first byte is zero, so EM < 2^2040 < n.
+JFSX_HD int encrypt(const Key &k, uint32_t e, const uint8_t *msg, int len, const uint8_t *seed,
+                    uint8_t ct[kModBytes]) {
+    if (len < 0 || len > kMaxMsg) {
+        for (int i = 0; i < kModBytes; i++) ct[i] = 0;
+        return -1;
+    }
+    uint8_t em[kModBytes];
+    oaep_encode(k.lhash, msg, len, seed, em);
+    uint32_t x[kNLimbs], r[kNLimbs];
+    from_be(em, kModBytes, x, kNLimbs);
+    mod_exp28_pub(x, e, k.n, k.ninv28, k.r2n28, r);
+    to_be(r, kNLimbs, ct, kModBytes);
+    return 0;
 }
 
 }  // namespace jfsx_rsa

@@ -1,4 +1,5 @@
-// jfsx_rsa.hip -- batched RSA-OAEP key unwrap on the GPU.
+// jfsx_rsa.hip -- batched RSA-OAEP key unwrap on the GPU, and
+// the key wrap, its write side (the last part of this file).
 //
 // rsaEncryptor.Decrypt (pkg/object/encrypt.go:124-134) runs once per object
 // the reference opens (encrypt.go:207-210): an RSA-2048 private operation of
@@ -133,6 +134,89 @@ void launch_rsa_unwrap(hipStream_t s, const void *key, int n, const uint8_t *ct,
     else
         hipLaunchKernelGGL(rsa_half_k, dim3(gh, 2), dim3(kRsaLanes), 0, s, (const jfsx_rsa::Key *)key, n, ct, mh);
     hipLaunchKernelGGL(rsa_finish_k, dim3(g), dim3(64), 0, s, (const jfsx_rsa::Key *)key, n, ct, mh, em, len);
+}
+
+// ---------------------------------------------------------------------------
+// The key wrap, the write side (rsaEncryptor.Encrypt, encrypt.go:128-130,
+// called per object at :169): rsa.EncryptOAEP(sha256, rand, pub, key, label)
+// for a whole upload window.
+//   * rsa_encode_k: one thread per item: EME-OAEP encoding with the caller's
+//     seed into the workspace, as 64 32-bit limbs (rsa_finish_k in reverse).
+//     An item longer than the OAEP capacity encodes as zero, which the
+//     exponentiation maps to 256 zero bytes.
+//   * rsa_wrap_k: the four lanes of a DPP quad per item: EM^e mod n by
+//     jfsx_rsa.h's mod_exp28_pub_quad, then 256 big-endian bytes, a quarter
+//     from each lane.
+// No branch and no address depends on the data key or the seed; e and the
+// message lengths are public.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void rsa_encode_k(const jfsx_rsa::Key *__restrict__ key, int n,
+                                                   const uint8_t *__restrict__ msg, const uint32_t *__restrict__ len,
+                                                   const uint8_t *__restrict__ seed, uint32_t *__restrict__ em_out) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    uint32_t *o = em_out + (size_t)jfsx_rsa::kNLimbs * i;
+    const uint32_t l = len[i];
+    if (l > (uint32_t)jfsx_rsa::kMaxMsg) {  // "message too long for RSA key size"
+        for (int j = 0; j < jfsx_rsa::kNLimbs; j++) o[j] = 0;
+        return;
+    }
+    uint8_t em[kModBytes];
+    jfsx_rsa::oaep_encode(key->lhash, msg + (size_t)kRsaWrapSlot * i, (int)l, seed + (size_t)jfsx_rsa::kHash * i, em);
+    uint32_t x[jfsx_rsa::kNLimbs];
+    jfsx_rsa::from_be(em, kModBytes, x, jfsx_rsa::kNLimbs);
+    for (int j = 0; j < jfsx_rsa::kNLimbs; j++) o[j] = x[j];
+}
+
+// the lane exchange of mod_exp28_pub_quad: the quad is lanes (4k .. 4k+3);
+// DPP quad_perm broadcasts (K,K,K,K) and the cyclic shifts (1,2,3,0) / (3,0,1,2)
+struct QuadDpp {
+    uint32_t lane;
+    __device__ __forceinline__ static constexpr bool tracing() { return false; }
+    template <int K>
+    __device__ __forceinline__ uint32_t from(uint32_t v) const {
+        return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, K * 0x55, 0xF, 0xF, true);
+    }
+    __device__ __forceinline__ uint32_t next(uint32_t v) const {
+        return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x39, 0xF, 0xF, true);
+    }
+    __device__ __forceinline__ uint32_t prev(uint32_t v) const {
+        return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x93, 0xF, 0xF, true);
+    }
+};
+
+// threads 4i .. 4i+3 of the grid: item i (16 items per workgroup).  Quads
+// never straddle a bound: all four lanes see the same i.
+__global__ __launch_bounds__(64) void rsa_wrap_k(const jfsx_rsa::Key *__restrict__ key, uint32_t e, int n,
+                                                 const uint32_t *__restrict__ em, uint8_t *__restrict__ ct) {
+    const int t = blockIdx.x * 64 + threadIdx.x, i = t >> 2;
+    if (i >= n) return;
+    const uint32_t lane = (uint32_t)(t & 3);
+    const QuadDpp x{lane};
+    const jfsx_rsa::Key &k = *key;
+    uint32_t r[jfsx_rsa::kNLimbs];
+    jfsx_rsa::mod_exp28_pub_quad(x, em + (size_t)jfsx_rsa::kNLimbs * i, e, k.n, k.ninv28, k.r2n28, r);
+    // lane L stores limbs 16 L .. 16 L + 15: limb w is bytes 252 - 4w .. 255 - 4w
+    uint32_t *o = (uint32_t *)(ct + (size_t)kModBytes * i);
+    constexpr int Q = jfsx_rsa::kNLimbs / 4;
+    // (picked with masks behind a register barrier: a select on the lane would
+    // become an indexed read of r, and r would live in scratch memory)
+    uint32_t odd = 0u - (lane & 1u), upper = 0u - (lane >> 1);
+    JFSX_RSA_OPAQUE(odd);
+    JFSX_RSA_OPAQUE(upper);
+#pragma unroll
+    for (int j = 0; j < Q; j++) {
+        const uint32_t lo = (r[j] & ~odd) | (r[Q + j] & odd), hi = (r[2 * Q + j] & ~odd) | (r[3 * Q + j] & odd);
+        o[jfsx_rsa::kNLimbs - 1 - ((int)lane * Q + j)] = __builtin_bswap32((lo & ~upper) | (hi & upper));
+    }
+}
+
+void launch_rsa_wrap(hipStream_t s, const void *key, uint32_t e, int n, const uint8_t *msg, const uint32_t *len,
+                     const uint8_t *seed, uint32_t *em, uint8_t *ct) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(rsa_encode_k, dim3((n + 63) / 64), dim3(64), 0, s, (const jfsx_rsa::Key *)key, n, msg, len,
+                       seed, em);
+    hipLaunchKernelGGL(rsa_wrap_k, dim3((n + 15) / 16), dim3(64), 0, s, (const jfsx_rsa::Key *)key, e, n, em, ct);
 }
 
 }  // namespace jfsx

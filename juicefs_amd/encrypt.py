@@ -5,15 +5,20 @@ Same names, argument meaning and error behaviour as the reference:
   Encryptor                  interface {Encrypt, Decrypt}            encrypt.go:38-41
   ParseRsaPrivateKeyFromPem  PEM (PKCS#1/PKCS#8, optional passphrase) encrypt.go:66-107
   NewRSAEncryptor            RSA-OAEP(SHA-256, label "keys")          encrypt.go:124-134
+  RsaEncryptor.EncryptBatch  Encrypt / Decrypt for a whole window     encrypt.go:128-134
+    / DecryptBatch           on the GPU
   NewDataEncryptor           "" / "aes256gcm-rsa" / "chacha20-rsa"    encrypt.go:142-162
   DataEncryptor.Encrypt      random key+nonce, wrap, header, Seal    encrypt.go:164-194
   DataEncryptor.Decrypt      header parse, unwrap, Open              encrypt.go:196-216
   NewEncrypted / Encrypted   object-store wrapper (Get/Put)          encrypt.go:218-267
 
-The AEAD work (Seal/Open) runs on the HIP engine (libjfsx.so); RSA-OAEP key
-wrapping stays on the host, as it does in the reference, through OpenSSL's
-libcrypto.  DataEncryptor.EncryptBatch / DecryptBatch are the batched entry
-points an upload/download worker pool uses (one engine call per batch).
+The AEAD work (Seal/Open) runs on the HIP engine (libjfsx.so).  RSA-OAEP key
+wrapping goes through OpenSSL's libcrypto on the host, as in the reference, or
+for a whole window at once on the engine: RsaEncryptor.DecryptBatch (always
+used by DataEncryptor.DecryptBatch) and RsaEncryptor.EncryptBatch (used by
+DataEncryptor(wrap="gpu")).  DataEncryptor.EncryptBatch / DecryptBatch are the
+batched entry points an upload/download worker pool uses (one engine call per
+batch).
 """
 import ctypes
 import ctypes.util
@@ -177,6 +182,22 @@ def rsa_crt_components(priv, nbytes=128):
     return tuple(out)
 
 
+def rsa_public_exponent(priv):
+    """The public exponent e of an RSA key (Go's PublicKey.E)."""
+    L = _Crypto.get().L
+    bn = ctypes.c_void_p()
+    if L.EVP_PKEY_get_bn_param(priv._pkey, b"e", ctypes.byref(bn)) != 1:
+        L.ERR_clear_error()
+        raise EncryptError("not an RSA key")
+    try:
+        buf = ctypes.create_string_buffer(8)
+        if L.BN_bn2binpad(bn, buf, 8) != 8:
+            raise EncryptError("RSA public exponent does not fit 8 bytes")
+        return int.from_bytes(buf.raw, "big")
+    finally:
+        L.BN_free(bn)
+
+
 class RsaEncryptor:
     """rsaEncryptor: RSA-OAEP with SHA-256 (OAEP and MGF1) and label "keys"."""
 
@@ -240,6 +261,31 @@ class RsaEncryptor:
         res = eng.oaep_decrypt_batch(dk, ciphertexts)
         return [EncryptError("crypto/rsa: decryption error") if r is None else r for r in res]
 
+    def EncryptBatch(self, plaintexts, eng=None, rand=os.urandom):
+        """Encrypt for a whole upload window at once: the engine's batched
+        RSA-OAEP wrap on the GPU with the key's public exponent, one 32-byte
+        OAEP seed per item from rand (what rsa.EncryptOAEP reads from its
+        random source), in order.  Returns, per item, the 256-byte ciphertext
+        or the EncryptError Encrypt would raise.  Keys the engine does not
+        take (not RSA-2048, or e outside 2 .. 2^31 - 1) wrap on the host one
+        by one, as the reference does (encrypt.go:128-130); rand is then not
+        read."""
+        eng = eng or default_engine()
+        dk = self._device_key(eng)
+        e = rsa_public_exponent(self.privKey) if dk is not None else 0
+        if dk is None or not 2 <= e <= 0x7FFFFFFF:
+            out = []
+            for p in plaintexts:
+                try:
+                    out.append(self.Encrypt(p))
+                except EncryptError as err:
+                    out.append(err)
+            return out
+        msgs = [bytes(p) for p in plaintexts]
+        seeds = [rand(32) for _ in msgs]
+        res = eng.oaep_encrypt_batch(dk, msgs, seeds, e)
+        return [EncryptError("crypto/rsa: message too long") if r is None else r for r in res]
+
     def _device_key(self, eng):
         keys = self.__dict__.setdefault("_dev_keys", {})
         if eng.ctx not in keys:
@@ -263,10 +309,22 @@ class DataEncryptor:
 
     keyLen = 32
 
-    def __init__(self, keyEncryptor, algo, eng=None, rand=os.urandom, agg=None):
+    def __init__(self, keyEncryptor, algo, eng=None, rand=os.urandom, agg=None, wrap="host"):
         """agg: an engine.Aggregator; one-object Encrypt/Decrypt calls made
         concurrently from many threads (the reference's per-goroutine calls)
-        are then coalesced into engine batches."""
+        are then coalesced into engine batches.
+
+        wrap: where EncryptBatch wraps the object keys.  "host": one
+        keyEncryptor.Encrypt per object (the key encryptor draws its own OAEP
+        randomness); per object, rand gives the key, then the nonce.  "gpu":
+        keyEncryptor.EncryptBatch wraps the whole batch in one engine call
+        before the Seal; per object, rand gives the key, the 32-byte OAEP
+        seed, then the nonce."""
+        if wrap not in ("host", "gpu"):
+            raise ValueError("wrap is \"host\" or \"gpu\"")
+        if wrap == "gpu" and not hasattr(keyEncryptor, "EncryptBatch"):
+            raise ValueError("wrap=\"gpu\" needs a key encryptor with EncryptBatch")
+        self.wrap = wrap
         self.keyEncryptor = keyEncryptor
         self.algo = algo
         self._eng = eng
@@ -293,11 +351,8 @@ class DataEncryptor:
         result is a list of (object, checksum string)."""
         import numpy as np
         specs, outs, hdrs, segs = [], [], [], []
-        for p in plaintexts:
+        for p, (key, cipherkey, nonce) in zip(plaintexts, self.draw_keys(len(plaintexts))):
             p = bytes(p)
-            key = self._rand(self.keyLen)
-            cipherkey = self.keyEncryptor.Encrypt(key)
-            nonce = self._rand(12)
             hdr = bytes([len(cipherkey) >> 8, len(cipherkey) & 0xFF, len(nonce)]) + cipherkey + nonce
             src = np.frombuffer(p, np.uint8).copy() if p else np.zeros(1, np.uint8)
             dst = np.empty(max(len(p), 1), np.uint8)
@@ -323,6 +378,26 @@ class DataEncryptor:
             return objs
         return [(objs[i], str(self.eng.object_crc32c(hdrs[i], segs[i], outs[i][2], bytes(arr[i].tag))))
                 for i in range(n)]
+
+    def draw_keys(self, n):
+        """(key, wrapped key, nonce) for n objects, drawn from rand object by
+        object in dataEncryptor.Encrypt's order (encrypt.go:165-180); with
+        wrap="gpu" each object's OAEP seed is drawn between its key and its
+        nonce and all keys are wrapped in one engine call."""
+        if self.wrap == "host":
+            out = []
+            for _ in range(n):
+                key = self._rand(self.keyLen)
+                cipherkey = self.keyEncryptor.Encrypt(key)
+                out.append((key, cipherkey, self._rand(12)))
+            return out
+        drawn = [(self._rand(self.keyLen), self._rand(32), self._rand(12)) for _ in range(n)]
+        seeds = iter([s for _, s, _ in drawn])
+        wrapped = self.keyEncryptor.EncryptBatch([k for k, _, _ in drawn], self.eng, rand=lambda _n: next(seeds))
+        for w in wrapped:
+            if isinstance(w, Exception):
+                raise w
+        return [(k, w, nonce) for (k, _, nonce), w in zip(drawn, wrapped)]
 
     def DecryptBatch(self, ciphertexts, checksums=None):
         """Returns, per object, the plaintext or the exception Decrypt would
@@ -413,11 +488,11 @@ class DataEncryptor:
         return res
 
 
-def NewDataEncryptor(keyEncryptor, algo, eng=None, agg=None):
+def NewDataEncryptor(keyEncryptor, algo, eng=None, agg=None, wrap="host"):
     """encrypt.go:147-162."""
     if algo not in _ALGO:
         raise EncryptError("unsupport cipher: %s" % algo)
-    return DataEncryptor(keyEncryptor, _ALGO[algo], eng, agg=agg)
+    return DataEncryptor(keyEncryptor, _ALGO[algo], eng, agg=agg, wrap=wrap)
 
 
 # ---------------------------------------------------------------------------

@@ -40,7 +40,7 @@ EXPORTS = [
     "jfsx_seal_batch", "jfsx_open_batch", "jfsx_crc32c_segments", "jfsx_checksum", "jfsx_cache_verify",
     "jfsx_data_encrypt", "jfsx_data_decrypt", "jfsx_parse_header", "jfsx_gen_synthetic", "jfsx_gen_key",
     "jfsx_debug_tables", "jfsx_crc32c_update", "jfsx_crc32c_combine", "jfsx_object_crc32c",
-    "jfsx_rsa_key_new", "jfsx_rsa_key_free", "jfsx_rsa_oaep_decrypt_batch",
+    "jfsx_rsa_key_new", "jfsx_rsa_key_free", "jfsx_rsa_oaep_decrypt_batch", "jfsx_rsa_oaep_encrypt_batch",
     "jfsx_seal_batch_async", "jfsx_open_batch_async", "jfsx_crc32c_segments_async", "jfsx_wait",
     "jfsx_agg_new", "jfsx_agg_free", "jfsx_agg_seal", "jfsx_agg_open", "jfsx_agg_crc32c", "jfsx_agg_stats",
     "jfsx_gen_synthetic_batch", "jfsx_mctx_open", "jfsx_mctx_close", "jfsx_mctx_ndev", "jfsx_mctx_ctx",
@@ -214,6 +214,7 @@ def load_library(path=LIB_PATH):
             "jfsx_rsa_key_new": (I, [P, P, P, P, P, P, I, P, I, PP]),
             "jfsx_rsa_key_free": (I, [P]),
             "jfsx_rsa_oaep_decrypt_batch": (I, [P, P, I, P, U64, P, P, U64, P]),
+            "jfsx_rsa_oaep_encrypt_batch": (I, [P, P, U32, I, P, U64, P, P, P, U64, P]),
             "jfsx_seal_batch_async": (I, [P, I, I, ctypes.POINTER(jfsx_blk), I, I, ctypes.POINTER(U64)]),
             "jfsx_open_batch_async": (I, [P, I, I, ctypes.POINTER(jfsx_blk), I, I, ctypes.POINTER(U64)]),
             "jfsx_crc32c_segments_async": (I, [P, I, ctypes.POINTER(jfsx_range), I, I, ctypes.POINTER(U64)]),
@@ -890,6 +891,31 @@ class Engine:
                                                        msg.ctypes.data, 256, mlen.ctypes.data),
                     "jfsx_rsa_oaep_decrypt_batch")
         return [None if mlen[i] < 0 else msg[256 * i:256 * i + mlen[i]].tobytes() for i in range(n)]
+
+    def oaep_encrypt_batch(self, key, msgs, seeds, e=65537):
+        """rsa.EncryptOAEP(sha256, rand, pub, m, label) for every m at once,
+        with the 32 bytes Go would read from rand given per item (seeds) and
+        the public exponent e: a list of 256-byte ciphertexts, None where Go
+        returns "message too long for RSA key size"."""
+        n = len(msgs)
+        if len(seeds) != n or any(len(s) != 32 for s in seeds):
+            raise ValueError("oaep_encrypt_batch takes one 32-byte seed per message")
+        if n == 0:
+            return []
+        stride = max(1, max(len(m) for m in msgs))
+        buf = np.zeros(n * stride, np.uint8)
+        lens = np.zeros(n, np.uint32)
+        for i, m in enumerate(msgs):
+            m = bytes(m)
+            buf[i * stride:i * stride + len(m)] = np.frombuffer(m, np.uint8)
+            lens[i] = len(m)
+        sd = np.frombuffer(b"".join(bytes(s) for s in seeds), np.uint8)
+        ct = np.zeros(n * 256, np.uint8)
+        st = np.zeros(n, np.int32)
+        self._check(self.L.jfsx_rsa_oaep_encrypt_batch(self.ctx, key, e, n, buf.ctypes.data, stride, lens.ctypes.data,
+                                                       sd.ctypes.data, ct.ctypes.data, 256, st.ctypes.data),
+                    "jfsx_rsa_oaep_encrypt_batch")
+        return [None if st[i] < 0 else ct[256 * i:256 * i + 256].tobytes() for i in range(n)]
 
     def crc32c_update(self, crc, data):
         return crc32c_update(crc, data)
