@@ -21,6 +21,9 @@
  *   (+ JFSX_CRC_CT)      stored object, fused with Seal/Open        (s3.go:140-146,173-176)
  *   jfsx_load_batch      cachedStore.load's Decrypt + Decompress +  pkg/chunk/cached_store.go:673-748
  *                        bcache.cache's checksum(), one call        (disk_cache.go:433-483)
+ *   jfsx_load_objects    the same from the stored object: the       pkg/object/checksum.go:55-82,
+ *                        store's checksum verify, Decrypt with its  encrypt.go:196-216, :132-134
+ *                        key unwrap, Decompress, checksum()
  *   jfsx_store_batch     uploadStagingFile's verified re-read +     pkg/chunk/cached_store.go:944-999, :371-413
  *                        upload's Compress + Encrypt + checksums,   (disk_cache.go:433-483, checksum.go:31-53)
  *                        one call
@@ -652,6 +655,83 @@ typedef struct jfsx_sblk {
     uint32_t crc_got, crc_expect;
 } jfsx_sblk;
 int jfsx_store_batch(jfsx_ctx *ctx, int algo, int codec, int n, jfsx_sblk *blks, int crc_mode, int mem);
+
+/* One-call object load: the whole read miss (cachedStore.load,
+ * pkg/chunk/cached_store.go:673-748) from the stored object to the page -- the
+ * object store's checksum verify (checksumReader, pkg/object/checksum.go:55-82),
+ * dataEncryptor.Decrypt with its key unwrap (encrypt.go:196-216; rsaEncryptor
+ * .Decrypt, :132-134), Decompress into the page (cached_store.go:738) and
+ * bcache.cache's checksum() (disk_cache.go:433-483) -- for a batch of objects in
+ * one synchronous call.  It is jfsx_load_batch with the two steps a reader ran
+ * around it moved onto the device: the wrapped data keys go up once and the
+ * unwrapped keys are handed from the RSA kernels to the AEAD key setup in
+ * device memory (no unwrapped key is ever copied to the host, and neither the
+ * call nor the record has an output that carries one), and the object checksum
+ * is folded from the segment CRCs of the uploaded image before Open runs on it.
+ * The call waits once.  A decoder is never started on bytes of a block that
+ * failed its checksum, its header, its key unwrap or its tag.
+ *   key       jfsx_rsa_key_new's key on ctx's device with a cipher; NULL with
+ *             JFSX_CIPHER_NONE
+ *   algo      JFSX_AES256GCM, JFSX_CHACHA20P1305, or JFSX_CIPHER_NONE (hdr_len
+ *             must then be 0)
+ *   codec     JFSX_CODEC_LZ4, JFSX_CODEC_ZSTD, or JFSX_CODEC_NONE for a volume
+ *             without --compress: src_len == len, a cipher is required (with
+ *             neither there is nothing but jfsx_crc32c_segments to run), and
+ *             Open writes the page itself
+ *   crc_mode  JFSX_CRC_NONE or JFSX_CRC_GEN for the page, with JFSX_CRC_CT
+ *             OR'ed in or given alone: the object checksum CRC32C(hdr || src ||
+ *             tag) -- without a cipher CRC32C(src) -- is computed into obj_crc
+ *             and compared with expect_crc
+ *   mem       as jfsx_load_batch; in addition, with JFSX_MEM_DEVICE, src is
+ *             16-byte aligned when JFSX_CRC_CT reads it, and dst is 16-byte
+ *             aligned with JFSX_CODEC_NONE (Open writes it).  hdr and tag are
+ *             host memory in both modes.
+ * Limits are those of jfsx_load_batch.  Any argument error is JFSX_EINVAL
+ * before anything runs, with the records untouched: the above, reserved != 0,
+ * hdr_len != 0 with a NULL hdr, a key of another device.
+ * Per-block result, the first rule that applies (the order the reference
+ * fails: checksum.go:55-70, encrypt.go:196-216, cached_store.go:738-743):
+ *   1 JFSX_CRC_CT: obj_crc != expect_crc               JFSX_ECRC
+ *   2 cipher: hdr_len < 3 or != 3 + klen + nlen        JFSX_EHEADER
+ *   3 cipher: the unwrap fails (also klen == 0,        JFSX_EKEY, key_len -1
+ *     klen > 256, c >= n), or gives a message that     JFSX_EKEY, key_len = its length
+ *     is not 32 bytes long
+ *   4 cipher: nlen != 12, or the tag does not verify   JFSX_ETAG
+ *   5 the decoder and length rows of jfsx_load_batch   JFSX_EFORMAT / JFSX_EDSTSIZE / JFSX_ESHORT
+ * out_len is as in jfsx_load_batch (0 for rules 1-4).  On any status other than
+ * JFSX_OK the page and the CRC array are all zero.  obj_crc is the computed
+ * value whenever JFSX_CRC_CT is set.  key_len is what the unwrap returned for
+ * the block (32 for a good one, -1 for the decryption error), and 0 where none
+ * ran for it: JFSX_CIPHER_NONE, or a header that names no key (rule 2).
+ * jfsx_metrics counts what the separate calls would: open_* over the blocks
+ * that reached Open with their own key (rules 1-3 passed; open_fail: rule 4),
+ * lz4d_* / zstdd_* over the blocks that reached the decoder (rules 1-4 passed),
+ * crc_* over the n pages with JFSX_CRC_GEN and, with JFSX_CRC_CT, over the n
+ * images as jfsx_crc32c_segments would (crc_fail: rule 1). */
+#define JFSX_CODEC_NONE 0   /* jfsx_load_objects only: the volume has no --compress */
+#define JFSX_EKEY    7      /* per-block: "decryt key: crypto/rsa: decryption error" (encrypt.go:207-210),
+                               or an unwrapped key that is not 32 bytes (NewCipher's key size error) */
+#define JFSX_EHEADER 8      /* per-block: "misformed ciphertext: %d %d" (encrypt.go:199-201) */
+typedef struct jfsx_oblk {
+    const void *hdr;      /* HOST memory, both mem modes: BE16(klen) | nlen | wrapped key | nonce */
+    uint32_t hdr_len;     /* 0 with JFSX_CIPHER_NONE                          */
+    uint32_t reserved;    /* must be 0                                        */
+    uint8_t tag[16];      /* in: the object's last 16 bytes; ignored with JFSX_CIPHER_NONE */
+    const void *src;      /* C: the object after the header, without the tag (or the stored block itself) */
+    uint64_t src_len;
+    void *dst;            /* the page                                         */
+    uint64_t len;
+    uint8_t *crc;         /* CRC_GEN: out, 4*max(1,ceil(len/32K)) bytes       */
+    uint32_t expect_crc;  /* in with JFSX_CRC_CT: the store's checksum of hdr || src || tag */
+    uint32_t obj_crc;     /* out with JFSX_CRC_CT: the value computed         */
+    uint64_t out_len;     /* out                                              */
+    int32_t status;       /* out                                              */
+    int32_t codec_info;   /* out, as jfsx_lblk                                */
+    int32_t key_len;      /* out: unwrapped key length, -1 decryption error, 0 when no unwrap ran */
+    int32_t reserved2;
+} jfsx_oblk;
+int jfsx_load_objects(jfsx_ctx *ctx, const jfsx_rsa_key *key, int algo, int codec, int n,
+                      jfsx_oblk *blks, int crc_mode, int mem);
 
 /* header helper: returns wrapped-key length and offset/size of the nonce so a
  * caller can unwrap the key first (encrypt.go:197-205) */

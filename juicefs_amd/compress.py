@@ -359,6 +359,125 @@ def load_blocks_fused(store, keys, lengths, compressor, enc=None, checksums=True
     return (pages, crcs) if checksums else pages
 
 
+def load_objects_fused(store, keys, lengths, compressor, enc, checksums=True, object_checksums=None):
+    """cachedStore.load for a batch in one engine call that starts at the stored
+    object (jfsx_load_objects): the object store's checksum verify
+    (checksumReader, checksum.go:55-82; object_checksums[i] is the decimal
+    string the store kept for keys[i], or None), the header parse and the
+    data-key unwrap, Open, Decompress and checksum() run back to back on the
+    device, and no unwrapped data key comes back to the host.  enc is the
+    volume's DataEncryptor, or None for a volume without one; compressor may be
+    the "none" compressor when enc is given.
+
+    Returns what load_blocks_fused returns and raises what it raises, in its
+    order: first, in key order, a checksum mismatch (ChecksumVerifyError, the
+    store's read error, which precedes Decrypt); then a decrypt failure of any
+    object; then, in key order, "read %s fully: %s (%d < %d)".  Without a codec
+    that is what load_blocks(NewEncrypted(store, enc), ...) gives.  An RSA key
+    the engine does not take (not RSA-2048 with CRT parameters) goes through
+    load_blocks_fused / DataEncryptor.DecryptBatch instead."""
+    from .checksum import ChecksumVerifyError, parse_checksum
+    from .encrypt import _ERR_OPEN, EncryptError
+    coded = isinstance(compressor, (LZ4, ZStandard))
+    if enc is None and not coded:
+        raise ValueError("load_objects_fused needs a cipher or the lz4 / zstd compressor")
+    lz4 = isinstance(compressor, LZ4)
+    codec = E.CODEC_NONE if not coded else E.CODEC_LZ4 if lz4 else E.CODEC_ZSTD
+    empty = "decompress an empty input" if lz4 else "Bytes slice is empty"
+    eng = compressor.eng if coded else enc.eng
+    keys, lengths = list(keys), [int(n) for n in lengths]
+    objs = [bytes(store.Get(k, 0, -1)) for k in keys]
+    want = [parse_checksum(object_checksums[i]) if object_checksums is not None else None for i in range(len(keys))]
+    verify = any(w is not None for w in want)
+    dk = None
+    if enc is not None:
+        dk = enc.keyEncryptor._device_key(eng) if hasattr(enc.keyEncryptor, "_device_key") else None
+        if dk is None:  # the engine refuses the key: unwrap on the host, as before
+            for o, w in zip(objs, want):
+                if w is not None and E.crc32c_update(0, o) != w:
+                    raise ChecksumVerifyError(E.crc32c_update(0, o), w)
+            if coded:
+                return load_blocks_fused(store, keys, lengths, compressor, enc=enc, checksums=checksums)
+            pages = []
+            for k, n, r in zip(keys, lengths, enc.DecryptBatch(objs)):
+                if isinstance(r, Exception):
+                    raise EncryptError("Decrypt: %s" % r)
+                if len(r) < n:
+                    raise CompressError("read %s fully: %s (%d < %d)" % (k, None, len(r), n))
+                pages.append(r[:n])
+            return (pages, [eng.checksum(p) for p in pages]) if checksums else pages
+    algo = E.CIPHER_NONE if enc is None else enc.algo
+    # what the host decides before the call: objects too short to cut into
+    # header, C and tag (encrypt.go:199-201, and Open's length check)
+    early = [None] * len(keys)
+    items, plen = [None] * len(keys), list(lengths)
+    for i, (o, n) in enumerate(zip(objs, lengths)):
+        if enc is None:
+            items[i] = o
+            continue
+        keyLen, nonceLen = ((o[0] << 8) + o[1], o[2]) if len(o) >= 3 else (0, 0)
+        h = 3 + keyLen + nonceLen
+        if len(o) < 3 or h >= len(o):
+            early[i] = "misformed ciphertext: %d %d" % (keyLen, nonceLen)
+        elif len(o) - h < 16:
+            early[i] = _ERR_OPEN[algo]  # runs after the unwrap in the reference; see below
+        else:
+            items[i] = (o[:h], o[h:-16], o[-16:])
+            if not coded:
+                plen[i] = len(o) - h - 16  # Open's output is the page; cut to the block's length below
+    run = [i for i in range(len(keys)) if early[i] is None and not (enc is None and len(objs[i]) == 0)]
+    res = [None] * len(keys)
+    info = [None] * len(keys)
+    if run:
+        # the verify is batch-wide: an object the store kept no checksum for is given its own
+        expect = [want[i] if want[i] is not None else E.crc32c_update(0, objs[i]) for i in run] if verify else None
+        got = eng.load_objects(dk, algo, codec, [items[i] for i in run], [plen[i] for i in run], crc=checksums,
+                               expect=expect)
+        for j, i in enumerate(run):
+            res[i], info[i] = got[j], eng.load_info[j]
+    # 1. the store's read: checksum mismatches, in key order
+    for i, o in enumerate(objs):
+        if want[i] is None:
+            continue
+        crc = info[i][3] if res[i] is not None else E.crc32c_update(0, o)
+        if crc != want[i]:
+            raise ChecksumVerifyError(crc, want[i])
+    # 2. Decrypt's failures before Open (header, key), then Open's
+    for i in range(len(keys)):
+        if early[i] is not None and early[i] != _ERR_OPEN[algo]:
+            raise EncryptError("Decrypt: %s" % early[i])
+        if res[i] is not None and res[i][0] == E.EHEADER:
+            o = objs[i]
+            raise EncryptError("Decrypt: misformed ciphertext: %d %d" % ((o[0] << 8) + o[1], o[2]))
+        if res[i] is not None and res[i][0] == E.EKEY:
+            kl = info[i][2]
+            raise EncryptError("Decrypt: %s" % ("decryt key: crypto/rsa: decryption error" if kl < 0
+                                                else "crypto/aes: invalid key size %d" % kl))
+    for i in range(len(keys)):
+        if early[i] is not None or (res[i] is not None and res[i][0] == E.ETAG):
+            raise EncryptError("Decrypt: %s" % _ERR_OPEN[algo])
+    # 3. Decompress and the length check, in key order
+    pages, crcs = [], []
+    for i, (k, n) in enumerate(zip(keys, lengths)):
+        if res[i] is None or (coded and enc is not None and len(items[i][1]) == 0):
+            raise CompressError("read %s fully: %s (%d < %d)" % (k, empty, 0, n))
+        st, page, crc = res[i]
+        if st == E.EDSTSIZE:
+            d = compressor.DecompressBatch([objs[i] if enc is None else enc.Decrypt(objs[i])], [n])[0]
+            raise CompressError("read %s fully: %s (%d < %d)" % (k, d, 0, n))
+        if st == E.EFORMAT:
+            raise CompressError("read %s fully: %s (%d < %d)"
+                                % (k, "lz4: malformed block" if lz4 else "zstd: corrupted frame", 0, n))
+        if st == E.ESHORT or len(page) < n:
+            raise CompressError("read %s fully: %s (%d < %d)" % (k, None, info[i][0] if coded else len(page), n))
+        if len(page) > n:  # no codec: the object holds more than the block's length
+            page = page[:n]
+            crc = eng.checksum(page) if checksums else None
+        pages.append(page)
+        crcs.append(crc)
+    return (pages, crcs) if checksums else pages
+
+
 def upload_blocks_fused(store, keys, blocks, compressor, enc=None, checksums=True):
     """cachedStore.upload for a batch in one engine call (jfsx_store_batch): each
     block is checksummed (bcache.stage's checksum(), disk_cache.go:433-483),

@@ -29,6 +29,7 @@
 #include "jfsx_rsa.h"
 #include "jfsx_md5.h"
 #include "jfsx_store.h"
+#include "jfsx_objload.h"
 
 using namespace jfsx;
 
@@ -438,6 +439,8 @@ struct jfsx_ctx {
     // load_stage the images and pages of a host batch, or the opened images of
     // a device batch.
     Workspace load_aead, load_crc;
+    Workspace obj_ct;  // jfsx_load_objects: the CRC stage over the stored images (JFSX_CRC_CT)
+    hipEvent_t obj_ev[2] = {};
     char *load_d = nullptr;
     size_t load_dcap = 0;
     char *load_h = nullptr;
@@ -706,10 +709,16 @@ int check_aead_args(int algo, int n, const jfsx_blk *blks, int crc_mode, bool de
 // main kernels, so a small batch's keysetup and finalize -- a few waves each,
 // latency-bound -- overlap the neighbouring batches' main kernels instead of
 // running between them.
+// key_hook (jfsx_load_objects): called on the keysetup's stream between the
+// descriptor upload and the keysetup kernel with the device KeyIn[n], for a
+// caller whose keys are already in device memory (the blocks' key fields are
+// then zero); null for everyone else.
+using KeyHook = std::function<void(hipStream_t, KeyIn *)>;
 int enqueue_aead(jfsx_ctx *c, Workspace &w, hipStream_t s, hipEvent_t k0, hipEvent_t k1, int algo, bool open, int n,
                  const jfsx_blk *blks, int crc_mode, hipStream_t up = nullptr, hipEvent_t up_ev = nullptr,
                  bool collect = true, hipStream_t fin = nullptr, hipEvent_t main_ev = nullptr,
-                 bool host_crc = false, bool zc = false, hipStream_t ksst = nullptr, hipEvent_t ks_ev = nullptr) {
+                 bool host_crc = false, bool zc = false, hipStream_t ksst = nullptr, hipEvent_t ks_ev = nullptr,
+                 const KeyHook *key_hook = nullptr) {
     const bool gcm = algo == JFSX_AES256GCM;
     // JFSX_CRC_BOTH: the AEAD kernels checksum the plaintext (CRC_GEN) into the
     // first half of each CRC array and crc_segments_k checksums the ciphertext
@@ -834,6 +843,7 @@ int enqueue_aead(jfsx_ctx *c, Workspace &w, hipStream_t s, hipEvent_t k0, hipEve
         HIP_OK(hipEventRecord(up_ev, up));
         HIP_OK(hipStreamWaitEvent(s, up_ev, 0));
     }
+    if (key_hook) (*key_hook)(ks, (KeyIn *)(d + o_keys));
     if (gcm) launch_gcm_keysetup(ks, n, dk, db, (GcmSched *)(d + o_sched), c->tabs, c->bitslice);
     else launch_cp_keysetup(ks, n, dk, db, (CpSched *)(d + o_sched));
     if (kss) {  // the descriptors and schedules are ready for the compute stream
@@ -2639,6 +2649,13 @@ int jfsx_ctx_open(int device, uint32_t flags, jfsx_ctx **out) {
             return JFSX_EIO;
         }
     }
+    for (hipEvent_t &e : c->obj_ev) {
+        if (hipEventCreate(&e) != hipSuccess) {
+            e = nullptr;
+            jfsx_ctx_close(c);
+            return JFSX_EIO;
+        }
+    }
     for (PipeSlot &p : c->pipe) {
         if (hipEventCreateWithFlags(&p.ev_in, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&p.ev_comp, hipEventDisableTiming) != hipSuccess ||
@@ -2675,10 +2692,12 @@ int jfsx_ctx_close(jfsx_ctx *c) {
     if (c->d_tab) (void)hipFree(c->d_tab);
     if (c->rsa_d) (void)hipFree(c->rsa_d);
     if (c->rsa_h) (void)hipHostFree(c->rsa_h);
-    for (Workspace *w : {&c->load_aead, &c->load_crc}) {
+    for (Workspace *w : {&c->load_aead, &c->load_crc, &c->obj_ct}) {
         if (w->d) (void)hipFree(w->d);
         if (w->h) (void)hipHostFree(w->h);
     }
+    for (hipEvent_t e : c->obj_ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->load_d) (void)hipFree(c->load_d);
     if (c->load_stage) (void)hipFree(c->load_stage);
     if (c->load_h) (void)hipHostFree(c->load_h);
@@ -3880,3 +3899,385 @@ int jfsx_rsa_oaep_encrypt_batch(jfsx_ctx *c, const jfsx_rsa_key *k, uint32_t e, 
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------
+// jfsx_load_objects: checksum verify -> key unwrap -> Open -> decompress ->
+// checksum() of a batch of stored objects in one call (checksumReader,
+// checksum.go:55-82; dataEncryptor.Decrypt, encrypt.go:196-216;
+// cachedStore.load, cached_store.go:673-748).  jfsx_load_batch's chain
+// (load_enqueue) with the two stages a reader ran around it in front, on the
+// same stream and in the same grow-only buffers; jfsx_objload.hip has the order
+// and the gate rule.  The host still plans everything from the lengths alone
+// and waits once.
+// ---------------------------------------------------------------------------
+namespace {
+
+int check_objects_args(const jfsx_rsa_key *key, int algo, int codec, int n, const jfsx_oblk *blks, int crc_mode,
+                       int mem) {
+    const bool cipher = algo != JFSX_CIPHER_NONE, coded = codec != JFSX_CODEC_NONE;
+    if (cipher && algo != JFSX_AES256GCM && algo != JFSX_CHACHA20P1305) return JFSX_EINVAL;
+    if (coded && codec != JFSX_CODEC_LZ4 && codec != JFSX_CODEC_ZSTD) return JFSX_EINVAL;
+    if (!cipher && !coded) return JFSX_EINVAL;  // jfsx_crc32c_segments serves that volume
+    if (crc_mode < 0 || (crc_mode & ~(JFSX_CRC_GEN | JFSX_CRC_CT))) return JFSX_EINVAL;
+    if (mem != JFSX_MEM_DEVICE && mem != JFSX_MEM_HOST) return JFSX_EINVAL;
+    if (n < 0 || cipher != (key != nullptr)) return JFSX_EINVAL;
+    const bool crc = (crc_mode & JFSX_CRC_GEN) != 0, ct = (crc_mode & JFSX_CRC_CT) != 0;
+    for (int i = 0; i < n; i++) {
+        const jfsx_oblk &b = blks[i];
+        if (b.reserved || (b.hdr_len && (!b.hdr || !cipher))) return JFSX_EINVAL;
+        if ((b.src_len && !b.src) || (b.len && !b.dst)) return JFSX_EINVAL;
+        if (!coded && b.src_len != b.len) return JFSX_EINVAL;
+        // check_load_args' limits
+        if (b.src_len > kLz4MaxInput || b.len >= ((uint64_t)1 << 32)) return JFSX_EINVAL;
+        if (codec == JFSX_CODEC_ZSTD && b.len >= ((uint64_t)1 << 31)) return JFSX_EINVAL;
+        if (crc && !b.crc) return JFSX_EINVAL;
+        if (mem == JFSX_MEM_DEVICE) {
+            // Open and the image CRC pass read src, Open (no codec) writes dst, the page CRC pass reads dst
+            if ((cipher || ct) && b.src_len && !aligned16(b.src)) return JFSX_EINVAL;
+            if ((crc || !coded) && b.len && !aligned16(b.dst)) return JFSX_EINVAL;
+            if (b.dst && b.dst == b.src) return JFSX_EINVAL;
+        }
+    }
+    return 0;
+}
+
+struct ObjLoadState {
+    char *bounce = nullptr;
+    size_t bcap = 0;
+    std::vector<size_t> poff;
+    std::vector<char> out_b;
+    size_t h_res = 0, st_off = 0, crc_off = 0;  // the download in load_h; ObjState[n] and CRC words behind LoadRes[n]
+    int zd_waves = 0;
+    bool aead = false, crc = false, ct = false, coded = false;
+};
+
+int objects_enqueue(jfsx_ctx *c, const jfsx_rsa_key *key, int algo, int codec, int n, const jfsx_oblk *blks,
+                    int crc_mode, bool host, ObjLoadState &st) {
+    hipStream_t s = c->stream;
+    const bool aead = st.aead = algo != JFSX_CIPHER_NONE;
+    const bool crc = st.crc = (crc_mode & JFSX_CRC_GEN) != 0;
+    const bool ct = st.ct = (crc_mode & JFSX_CRC_CT) != 0;
+    const bool coded = st.coded = codec != JFSX_CODEC_NONE;
+    const bool zstd = codec == JFSX_CODEC_ZSTD;
+    constexpr size_t K = jfsx_rsa::kModBytes;
+    std::vector<size_t> ioff(n);
+    st.poff.assign(n, 0);
+    st.out_b.assign(n, 0);
+    size_t img_bytes = 0, page_bytes = 0;
+    uint64_t crc_words = 0, ct_words = 0, max_len = 0;
+    for (int i = 0; i < n; i++) {
+        ioff[i] = img_bytes;
+        img_bytes += align256(blks[i].src_len);
+        st.poff[i] = page_bytes;
+        page_bytes += align256(blks[i].len);
+        crc_words += nseg_of(blks[i].len);
+        ct_words += nseg_of(blks[i].src_len);
+        max_len = std::max<uint64_t>(max_len, blks[i].len);
+    }
+    // device workspace: load_enqueue's, with ObjBlk behind LoadBlk (one upload)
+    // and ObjState behind LoadRes (one download)
+    size_t off = 0;
+    const size_t o_lb = off; off = align256(off + sizeof(LoadBlk) * n);
+    const size_t o_ob = off; off = align256(off + sizeof(ObjBlk) * n);
+    const size_t up = off;
+    const size_t o_z = off; off = align256(off + sizeof(ZDev) * n);
+    const size_t o_zo = off; off = align256(off + sizeof(ZOut) * n);
+    const size_t o_res = off; off = align256(off + sizeof(LoadRes) * n);
+    const size_t o_st = off; off = align256(off + sizeof(ObjState) * n);
+    const size_t o_crc = off; if (host && crc) off = align256(off + 4 * crc_words);
+    const size_t down = off - o_res;
+    const size_t o_ct = off; if (ct) off = align256(off + 4 * ct_words);
+    const size_t o_tab = off;
+    st.h_res = up;
+    st.st_off = o_st - o_res;
+    st.crc_off = o_crc - o_res;
+    // the unwrap's workspace, as jfsx_rsa_oaep_decrypt_batch lays it out
+    const size_t r_ct = 0, r_mh = align256(K * n), r_em = r_mh + align256(2 * 4 * jfsx_rsa::kLimbs * (size_t)n),
+                 r_len = r_em + align256(K * n), r_bytes = r_len + align256(4 * (size_t)n);
+    int rc;
+    // every buffer of the path before the first enqueue
+    if (zstd) {
+        st.zd_waves = zstd_decode_waves(c, n);
+        rc = ensure_zstd_decode(c, &c->load_d, &c->load_dcap, o_tab, n, &st.zd_waves);
+    } else {
+        rc = ensure_dev(c, &c->load_d, &c->load_dcap, o_tab);
+    }
+    if (rc) return rc;
+    if ((rc = ensure_host(&c->load_h, &c->load_hcap, up + down))) return rc;
+    // device memory without a codec: Open reads src and writes the page itself
+    const size_t stage_need = host ? img_bytes + page_bytes : (aead && coded) ? img_bytes : 0;
+    if (stage_need && (rc = ensure_dev(c, &c->load_stage, &c->load_scap, stage_need))) return rc;
+    if (aead) {
+        if ((rc = ensure_dev(c, &c->rsa_d, &c->rsa_dcap, r_bytes))) return rc;
+        if ((rc = ensure_host(&c->rsa_h, &c->rsa_hcap, align256(K * n)))) return rc;
+    }
+    char *d = c->load_d, *h = c->load_h, *stage = c->load_stage;
+    std::vector<char> in_b(n, 0);
+    bool all_in = host, all_out = host, any_in = false, any_out = false;
+    if (host) {
+        for (int i = 0; i < n; i++) {
+            if (blks[i].src_len) {
+                in_b[i] = !host_pinned(blks[i].src, blks[i].src_len);
+                all_in = all_in && in_b[i];
+                any_in = any_in || in_b[i];
+            }
+            if (blks[i].len) {
+                st.out_b[i] = !host_pinned(blks[i].dst, blks[i].len);
+                all_out = all_out && st.out_b[i];
+                any_out = any_out || st.out_b[i];
+            }
+        }
+        const size_t need = std::max(any_in ? img_bytes : 0, any_out ? page_bytes : 0);
+        if (need) {
+            if (!(st.bounce = bounce_get(c, need, &st.bcap))) return JFSX_ENOMEM;
+            std::vector<std::pair<char *, const char *>> cp;
+            std::vector<size_t> cl;
+            for (int i = 0; i < n; i++)
+                if (in_b[i]) {
+                    cp.push_back({st.bounce + ioff[i], (const char *)blks[i].src});
+                    cl.push_back(blks[i].src_len);
+                    c->bounce.bytes_in += blks[i].src_len;
+                }
+            par_copy(cp, cl);
+        }
+    }
+    // block records; the blocks of the image CRC, Open and page CRC stages; the wrapped keys
+    LoadBlk *hl = (LoadBlk *)(h + o_lb);
+    ObjBlk *ho = (ObjBlk *)(h + o_ob);
+    std::vector<jfsx_blk> ab(aead ? n : 0), cb(crc && coded ? n : 0), tb(ct ? n : 0);
+    uint64_t cw = 0, tw = 0;
+    for (int i = 0; i < n; i++) {
+        const jfsx_oblk &b = blks[i];
+        // raw: the stored bytes in device memory; img: what the decoder reads
+        uint8_t *raw = host ? (uint8_t *)(stage + ioff[i]) : (uint8_t *)b.src;
+        uint8_t *img = host || (aead && coded) ? (uint8_t *)(stage + ioff[i]) : (uint8_t *)b.src;
+        if (!b.src_len) raw = img = nullptr;
+        hl[i].img = img;
+        hl[i].dst = !b.len ? nullptr : host ? (uint8_t *)(stage + img_bytes + st.poff[i]) : (uint8_t *)b.dst;
+        hl[i].crc = !crc ? nullptr : host ? (uint8_t *)(d + o_crc + 4 * cw) : b.crc;
+        hl[i].src_len = b.src_len;
+        hl[i].len = b.len;
+        cw += nseg_of(b.len);
+        ObjBlk &o = ho[i];
+        memset(&o, 0, sizeof(o));
+        o.segs = ct ? (const uint8_t *)(d + o_ct + 4 * tw) : nullptr;
+        o.clen = b.src_len;
+        o.expect = b.expect_crc;
+        tw += nseg_of(b.src_len);
+        if (ct) {
+            jfsx_blk &k = tb[i];
+            memset(&k, 0, sizeof(k));
+            k.src = raw;
+            k.len = b.src_len;
+            k.crc = (uint8_t *)o.segs;
+        }
+        if (aead) {
+            // dataEncryptor.Decrypt's header parse (encrypt.go:197-205); the
+            // sizes that make the unwrap or Open fail without running are flags
+            const uint8_t *hd = (const uint8_t *)b.hdr;
+            uint8_t *w = (uint8_t *)c->rsa_h + K * i;
+            memset(w, 0, K);
+            jfsx_blk &a = ab[i];
+            memset(&a, 0, sizeof(a));
+            const uint32_t kl = b.hdr_len >= 3 ? ((uint32_t)hd[0] << 8) + hd[1] : 0, nl = b.hdr_len >= 3 ? hd[2] : 0;
+            if (b.hdr_len < 3 || b.hdr_len != 3 + kl + nl) {
+                o.flags |= jfsx_obj::kHdrBad;
+            } else {
+                if (kl == 0 || kl > K) o.flags |= jfsx_obj::kKeyBad;
+                else memcpy(w + K - kl, hd + 3, kl);  // a big-endian integer, left-padded
+                if (nl != 12) o.flags |= jfsx_obj::kNonceBad;
+                else memcpy(a.nonce, hd + 3 + kl, 12);
+            }
+            o.crc_hdr = jfsx_crc32c_update(0, hd, b.hdr_len);
+            o.crc_tag = jfsx_crc32c_update(0, b.tag, 16);
+            memcpy(a.tag, b.tag, 16);
+            a.src = raw;
+            a.dst = coded ? img : hl[i].dst;
+            a.len = b.src_len;
+            a.crc = coded ? nullptr : hl[i].crc;
+        }
+        if (crc && coded) {
+            jfsx_blk &k = cb[i];
+            memset(&k, 0, sizeof(k));
+            k.src = hl[i].dst;
+            k.len = b.len;
+            k.crc = hl[i].crc;
+        }
+    }
+    // 1. records, images (host) and wrapped keys up
+    HIP_OK(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemsetAsync(d + o_st, 0, sizeof(ObjState) * n, s));
+    if (host) {
+        if (all_in && img_bytes) {
+            HIP_OK(hipMemcpyAsync(stage, st.bounce, img_bytes, hipMemcpyHostToDevice, s));
+        } else {
+            for (int i = 0; i < n; i++)
+                if (blks[i].src_len)
+                    HIP_OK(hipMemcpyAsync(stage + ioff[i], in_b[i] ? st.bounce + ioff[i] : (const char *)blks[i].src,
+                                          blks[i].src_len, hipMemcpyHostToDevice, s));
+        }
+    }
+    char *r = c->rsa_d;
+    if (aead) HIP_OK(hipMemcpyAsync(r + r_ct, c->rsa_h, K * n, hipMemcpyHostToDevice, s));
+    const LoadBlk *dl = (const LoadBlk *)(d + o_lb);
+    const ObjBlk *dob = (const ObjBlk *)(d + o_ob);
+    ObjState *dst = (ObjState *)(d + o_st);
+    ZDev *dz = (ZDev *)(d + o_z);
+    ZOut *dzo = (ZOut *)(d + o_zo);
+    LoadRes *dres = (LoadRes *)(d + o_res);
+    // 2. segment CRCs of every image, before Open overwrites a host batch's in place
+    if (ct && (rc = enqueue_crc(c, c->obj_ct, s, c->obj_ev[0], c->obj_ev[1], n, tb.data(), JFSX_CRC_GEN, nullptr,
+                                nullptr, false)))
+        return rc;
+    // 3. the unwrap, 4. the fold
+    launch_begin();
+    if (aead)
+        launch_rsa_unwrap(s, key->d_key, n, (const uint8_t *)(r + r_ct), (uint32_t *)(r + r_mh), (uint8_t *)(r + r_em),
+                          (int32_t *)(r + r_len));
+    if (ct) launch_obj_fold(s, n, dob, aead ? 16 : 0, c->tabs.crcx + 64, dst);
+    HIP_OK(hipGetLastError());
+    // 5. the keys into Open's KeyIn[n], 6. Open: into the staging buffer for
+    // the decoder, or into the page with the fused CRC_GEN
+    const BlkOut *opened = nullptr;
+    if (aead) {
+        const KeyHook hook = [&](hipStream_t ks, KeyIn *dk) {
+            launch_obj_keys(ks, n, dob, dst, (uint8_t *)(r + r_em), (const int32_t *)(r + r_len), dk);
+        };
+        if ((rc = enqueue_aead(c, c->load_aead, s, c->load_ev[0], c->load_ev[1], algo, true, n, ab.data(),
+                               !coded && crc ? JFSX_CRC_GEN : JFSX_CRC_NONE, nullptr, nullptr, false, nullptr, nullptr,
+                               false, false, nullptr, nullptr, &hook)))
+            return rc;
+        opened = (const BlkOut *)c->load_aead.dout;
+    }
+    // 7. the gate and the decoder, then checksum() of every page
+    if (coded) {
+        launch_begin();
+        launch_obj_gate(s, n, dl, dob, dst, opened, ct, dz, dzo);
+        if (zstd) launch_zstd_decompress(s, n, dz, dzo, (uint8_t *)(d + o_tab), st.zd_waves);
+        else launch_lz4_decompress(s, n, dz, dzo);
+        HIP_OK(hipGetLastError());
+        if (crc && (rc = enqueue_crc(c, c->load_crc, s, c->load_ev[2], c->load_ev[3], n, cb.data(), JFSX_CRC_GEN,
+                                     nullptr, nullptr, false)))
+            return rc;
+    }
+    // 8. verdicts; pages and CRC arrays of failed blocks zeroed; one download
+    launch_begin();
+    const int groups = (int)std::min<uint64_t>(1024, std::max<uint64_t>(1, (max_len + 65535) / 65536));
+    launch_obj_verdict(s, n, dl, dob, dst, opened, coded ? dzo : nullptr, ct, zstd && st.zd_waves > 0, dres);
+    launch_load_wipe(s, n, groups, dl, dres, crc);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(h + st.h_res, d + o_res, down, hipMemcpyDeviceToHost, s));
+    if (host) {
+        const char *pages = stage + img_bytes;
+        if (all_out && page_bytes) {
+            HIP_OK(hipMemcpyAsync(st.bounce, pages, page_bytes, hipMemcpyDeviceToHost, s));
+        } else {
+            for (int i = 0; i < n; i++)
+                if (blks[i].len)
+                    HIP_OK(hipMemcpyAsync(st.out_b[i] ? st.bounce + st.poff[i] : (char *)blks[i].dst,
+                                          pages + st.poff[i], blks[i].len, hipMemcpyDeviceToHost, s));
+        }
+    }
+    return 0;
+}
+
+// Under c->mu for the whole call, as run_load.
+int run_objects(jfsx_ctx *c, const jfsx_rsa_key *key, int algo, int codec, int n, jfsx_oblk *blks, int crc_mode,
+                int mem) {
+    const bool host = mem == JFSX_MEM_HOST;
+    ObjLoadState st;
+    int rc = objects_enqueue(c, key, algo, codec, n, blks, crc_mode, host, st);
+    const hipError_t se = hipStreamSynchronize(c->stream);
+    for (Workspace *w : {&c->load_aead, &c->load_crc, &c->obj_ct}) {
+        if (!rc && se == hipSuccess && w->timed && w->nt) {
+            hipEvent_t *ev = w == &c->load_aead ? c->load_ev : w == &c->load_crc ? c->load_ev + 2 : c->obj_ev;
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) add_kernel_ms(c, ms);
+            else (void)hipGetLastError();
+        }
+        w->n = 0;
+        w->nt = 0;
+        w->timed = false;
+        w->crc_back = false;
+    }
+    if (!rc && se != hipSuccess) {
+        note_hip_error(se, __FILE__, __LINE__, "hipStreamSynchronize(load_objects)");
+        rc = JFSX_EIO;
+    }
+    if (!rc) {
+        const LoadRes *hr = (const LoadRes *)(c->load_h + st.h_res);
+        const ObjState *hs = (const ObjState *)(c->load_h + st.h_res + st.st_off);
+        const char *hw = c->load_h + st.h_res + st.crc_off;
+        std::vector<std::pair<char *, const char *>> cp;
+        std::vector<size_t> cl;
+        for (int i = 0; i < n; i++) {
+            jfsx_oblk &b = blks[i];
+            b.status = hr[i].status;
+            b.out_len = hr[i].out_len;
+            b.codec_info = hr[i].codec_info;
+            b.key_len = st.aead ? hs[i].key_len : 0;
+            if (st.ct) b.obj_crc = hs[i].obj_crc;
+            if (host && st.crc) {
+                memcpy(b.crc, hw, 4 * nseg_of(b.len));
+                hw += 4 * nseg_of(b.len);
+            }
+            if (host && st.out_b[i]) {
+                cp.push_back({(char *)b.dst, st.bounce + st.poff[i]});
+                cl.push_back(b.len);
+                c->bounce.bytes_out += b.len;
+            }
+        }
+        par_copy(cp, cl);
+    }
+    if (st.bounce) bounce_put(c, st.bounce, st.bcap);
+    if (rc) return rc;
+    // jfsx_ctx_metrics: what the separate calls would have counted
+    std::lock_guard<std::mutex> g(c->stat_mu);
+    jfsx_metrics &m = c->met;
+    const bool zstd = codec == JFSX_CODEC_ZSTD;
+    uint64_t &d_blocks = zstd ? m.zstdd_blocks : m.lz4d_blocks, &d_in = zstd ? m.zstdd_in : m.lz4d_in;
+    uint64_t &d_out = zstd ? m.zstdd_out : m.lz4d_out, &d_fail = zstd ? m.zstdd_fail : m.lz4d_fail;
+    if (st.aead) m.open_batches++;
+    m.crc_batches += (st.crc ? 1 : 0) + (st.ct ? 1 : 0);
+    for (int i = 0; i < n; i++) {
+        const jfsx_oblk &b = blks[i];
+        const bool keyed = b.status != JFSX_ECRC && b.status != JFSX_EHEADER && b.status != JFSX_EKEY;
+        if (st.aead && keyed) {
+            m.open_blocks++;
+            m.open_bytes += b.src_len;
+            m.open_fail += b.status == JFSX_ETAG;
+        }
+        if (st.coded && keyed && b.status != JFSX_ETAG) {  // the block reached the decoder
+            d_blocks++;
+            d_in += b.src_len;
+            d_out += b.out_len;
+            d_fail += b.status == JFSX_EFORMAT || b.status == JFSX_EDSTSIZE;
+            if (zstd && b.codec_info) m.zstd_serial++;
+        }
+        if (st.crc) {
+            m.crc_ranges++;
+            m.crc_bytes += b.len;
+        }
+        if (st.ct) {
+            m.crc_ranges++;
+            m.crc_bytes += b.src_len;
+            m.crc_fail += b.status == JFSX_ECRC;
+        }
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int jfsx_load_objects(jfsx_ctx *c, const jfsx_rsa_key *key, int algo, int codec, int n, jfsx_oblk *blks,
+                                 int crc_mode, int mem) {
+    if (!c || (n > 0 && !blks)) return JFSX_EINVAL;
+    // argument errors before the context or its device is touched
+    const int rc = check_objects_args(key, algo, codec, n, blks, crc_mode, mem);
+    if (rc || n == 0) return rc;
+    if (key && key->device != c->device) return JFSX_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    CtxScope es_(c);
+    HIP_OK(hipSetDevice(c->device));
+    return run_objects(c, key, algo, codec, n, blks, crc_mode, mem);
+}

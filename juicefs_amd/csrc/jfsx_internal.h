@@ -335,6 +335,38 @@ void launch_load_gate(hipStream_t s, int n, const LoadBlk *lb, const BlkOut *ope
 // use_fallback: ZOut.fallback is meaningful (the block-parallel zstd decoder ran)
 void launch_load_finish(hipStream_t s, int n, int wipe_groups, const LoadBlk *lb, const BlkOut *opened,
                         const ZOut *zo, bool use_fallback, bool crc_gen, LoadRes *res);
+// load_wipe_k alone, for a caller with a verdict kernel of its own
+void launch_load_wipe(hipStream_t s, int n, int wipe_groups, const LoadBlk *lb, const LoadRes *res, bool crc_gen);
+// One-call object load (jfsx_objload.hip): the kernels that put the object
+// checksum and the key unwrap in front of jfsx_load_batch's chain.  ObjBlk is
+// what the host knows of an object before anything runs; ObjState what the
+// device finds out (zeroed by the caller before the first kernel).
+struct ObjBlk {
+    const uint8_t *segs;  // JFSX_CRC_CT: the big-endian segment CRCs of the image (device), else null
+    uint64_t clen;        // src_len
+    uint32_t crc_hdr, crc_tag;  // crc32.Update(0, hdr) / (0, tag); 0 without a cipher
+    uint32_t expect;      // expect_crc
+    uint32_t flags;       // jfsx_obj::kHdrBad | kKeyBad | kNonceBad
+};
+struct ObjState {  // copied back to the host
+    uint32_t obj_crc;
+    uint32_t crc_bad;
+    int32_t key_len;
+    int32_t pad;
+};
+// one wave per object: obj_crc and obj_crc != expect into st; tail = bytes after the image (16 / 0)
+void launch_obj_fold(hipStream_t s, int n, const ObjBlk *ob, uint32_t tail, const uint32_t *x8pow, ObjState *st);
+// one thread per object: the 32-byte unwrap result of a block that passed
+// rules 1-3 into keys[i].key (zeros otherwise), key_len into st, the unwrap's
+// message slot (em, 256 bytes per object) zeroed
+void launch_obj_keys(hipStream_t s, int n, const ObjBlk *ob, ObjState *st, uint8_t *em, const int32_t *len,
+                     KeyIn *keys);
+// launch_load_gate / the verdict half of launch_load_finish with rules 1-4 in
+// front (jfsx_objload.h); opened null with JFSX_CIPHER_NONE, zo null with JFSX_CODEC_NONE
+void launch_obj_gate(hipStream_t s, int n, const LoadBlk *lb, const ObjBlk *ob, const ObjState *st,
+                     const BlkOut *opened, bool crc_ct, ZDev *z, ZOut *zo);
+void launch_obj_verdict(hipStream_t s, int n, const LoadBlk *lb, const ObjBlk *ob, const ObjState *st,
+                        const BlkOut *opened, const ZOut *zo, bool crc_ct, bool use_fallback, LoadRes *res);
 // One-call block store (jfsx_store.hip): the kernels around the compressor of
 // jfsx_store_batch.  StoreBlk: src = the page, dst = where the compressor
 // writes (cap bytes, the codec's bound of len), sink = kStoreSink bytes of

@@ -118,4 +118,10 @@ void launch_load_finish(hipStream_t s, int n, int wipe_groups, const LoadBlk *lb
                        crc_gen ? 1 : 0);
 }
 
+void launch_load_wipe(hipStream_t s, int n, int wipe_groups, const LoadBlk *lb, const LoadRes *res, bool crc_gen) {
+    if (n > 0)
+        hipLaunchKernelGGL(load_wipe_k, dim3(wipe_groups < 1 ? 1 : wipe_groups), dim3(kLoadThreads), 0, s, n, lb, res,
+                           crc_gen ? 1 : 0);
+}
+
 }  // namespace jfsx

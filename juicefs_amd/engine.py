@@ -29,6 +29,9 @@ EDSTSIZE = 5  # zstd: the output does not fit in dst_cap
 ESHORT = 6  # jfsx_load_batch: the image decoded to fewer bytes than the page ("read %s fully")
 CIPHER_NONE = -1  # jfsx_load_batch / jfsx_store_batch algo: the volume is not encrypted
 CODEC_LZ4, CODEC_ZSTD = 1, 2  # jfsx_load_batch / jfsx_store_batch codec
+CODEC_NONE = 0  # jfsx_load_objects only: the volume has no --compress
+EKEY = 7  # jfsx_load_objects: the data key does not unwrap, or is not 32 bytes long
+EHEADER = 8  # jfsx_load_objects: "misformed ciphertext" (the header does not describe itself)
 EINVAL, ENODEV, EIO, ENOMEM, EMISFORMED, EAGAIN = -22, -19, -5, -12, -74, -11
 SEG = 32 << 10
 
@@ -54,7 +57,7 @@ EXPORTS = [
     "jfsx_agg_data_encrypt", "jfsx_agg_data_decrypt",
     "jfsx_data_encrypt_ex", "jfsx_data_decrypt_ex", "jfsx_agg_data_encrypt_ex", "jfsx_agg_data_decrypt_ex",
     "jfsx_file_checksum_span", "jfsx_file_checksum_batch", "jfsx_file_checksum_fold",
-    "jfsx_load_batch", "jfsx_store_batch",
+    "jfsx_load_batch", "jfsx_store_batch", "jfsx_load_objects",
 ]
 
 
@@ -127,6 +130,17 @@ class jfsx_sblk(ctypes.Structure):
         ("hdr", ctypes.c_void_p), ("hdr_len", ctypes.c_uint32), ("obj_crc", ctypes.c_uint32),
         ("out_len", ctypes.c_uint64), ("status", ctypes.c_int32), ("crc_bad_seg", ctypes.c_int32),
         ("crc_got", ctypes.c_uint32), ("crc_expect", ctypes.c_uint32),
+    ]
+
+
+class jfsx_oblk(ctypes.Structure):
+    _fields_ = [
+        ("hdr", ctypes.c_void_p), ("hdr_len", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+        ("tag", ctypes.c_uint8 * 16), ("src", ctypes.c_void_p), ("src_len", ctypes.c_uint64),
+        ("dst", ctypes.c_void_p), ("len", ctypes.c_uint64), ("crc", ctypes.c_void_p),
+        ("expect_crc", ctypes.c_uint32), ("obj_crc", ctypes.c_uint32), ("out_len", ctypes.c_uint64),
+        ("status", ctypes.c_int32), ("codec_info", ctypes.c_int32), ("key_len", ctypes.c_int32),
+        ("reserved2", ctypes.c_int32),
     ]
 
 
@@ -251,6 +265,7 @@ def load_library(path=LIB_PATH):
             "jfsx_mctx_zstd_compress_batch": (I, [P, I, ctypes.POINTER(jfsx_zblk), I]),
             "jfsx_load_batch": (I, [P, I, I, I, ctypes.POINTER(jfsx_lblk), I, I]),
             "jfsx_store_batch": (I, [P, I, I, I, ctypes.POINTER(jfsx_sblk), I, I]),
+            "jfsx_load_objects": (I, [P, P, I, I, I, ctypes.POINTER(jfsx_oblk), I, I]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -676,6 +691,62 @@ class Engine:
         self.load_info = [(arr[i].out_len, arr[i].codec_info) for i in range(cnt)]
         return [(arr[i].status, page[:n].tobytes(), cbuf.tobytes() if crc else None)
                 for i, (_, page, cbuf, n) in enumerate(keep)]
+
+    # -- one-call object load (jfsx_load_objects) --------------------------
+    @staticmethod
+    def make_oblocks(specs):
+        """specs: iterable of dicts with src, src_len, dst, len, [hdr, hdr_len,
+        tag] (a cipher; hdr is host memory), [crc] (CRC_GEN), [expect_crc]
+        (CRC_CT); pointers as ints."""
+        specs = list(specs)
+        arr = (jfsx_oblk * max(len(specs), 1))()
+        for i, s in enumerate(specs):
+            b = arr[i]
+            b.hdr, b.hdr_len = s.get("hdr"), s.get("hdr_len", 0)
+            if s.get("tag") is not None:
+                ctypes.memmove(b.tag, bytes(s["tag"]), 16)
+            b.src, b.src_len = s.get("src"), s["src_len"]
+            b.dst, b.len = s.get("dst"), s["len"]
+            b.crc = s.get("crc")
+            b.expect_crc = s.get("expect_crc", 0)
+        return arr, len(specs)
+
+    def load_objects_batch(self, key, algo, codec, oblks, n, crc_mode=CRC_GEN, mem=MEM_DEVICE):
+        """The store's checksum verify, the data-key unwrap, Open, Decompress
+        and checksum() of n stored objects in one call.  key: rsa_key()'s handle
+        (None with CIPHER_NONE).  Per-block results in oblks[i].status (OK /
+        ECRC / EHEADER / EKEY / ETAG / EFORMAT / EDSTSIZE / ESHORT), .out_len,
+        .obj_crc, .key_len and .codec_info."""
+        self._check(self.L.jfsx_load_objects(self.ctx, key, algo, codec, n, oblks, crc_mode, mem),
+                    "jfsx_load_objects")
+
+    def load_objects(self, key, algo, codec, items, lengths, crc=True, expect=None):
+        """Host bytes in, host bytes out.  items: (hdr, C, tag) per object with
+        a cipher -- the stored object cut at its header's end and 16 bytes
+        before its own -- or the stored block itself with CIPHER_NONE; lengths:
+        the page length of each; expect: the store's checksum of each object
+        (asks for the verify).  Returns (status, page, crc bytes or None) per
+        block; self.load_info holds (out_len, codec_info, key_len, obj_crc)."""
+        specs, keep = [], []
+        for i, (it, n) in enumerate(zip(items, lengths)):
+            hdr, img, tag = (None, it, None) if algo == CIPHER_NONE else it
+            src = _u8(img)
+            hbuf = _u8(hdr) if hdr is not None else None
+            page = np.empty(max(int(n), 1), np.uint8)
+            cbuf = np.empty(4 * max(1, -(-int(n) // SEG)), np.uint8)
+            keep.append((src, hbuf, page, cbuf, int(n)))
+            specs.append({"hdr": hbuf.ctypes.data if hbuf is not None and hbuf.size else None,
+                          "hdr_len": hbuf.size if hbuf is not None else 0, "tag": tag,
+                          "src": src.ctypes.data if src.size else None, "src_len": src.size,
+                          "dst": page.ctypes.data if n else None, "len": int(n),
+                          "crc": cbuf.ctypes.data if crc else None,
+                          "expect_crc": int(expect[i]) if expect is not None else 0})
+        arr, cnt = self.make_oblocks(specs)
+        mode = (CRC_GEN if crc else CRC_NONE) | (CRC_CT if expect is not None else 0)
+        self.load_objects_batch(key, algo, codec, arr, cnt, mode, MEM_HOST)
+        self.load_info = [(arr[i].out_len, arr[i].codec_info, arr[i].key_len, arr[i].obj_crc) for i in range(cnt)]
+        return [(arr[i].status, page[:n].tobytes(), cbuf.tobytes() if crc else None)
+                for i, (_, _, page, cbuf, n) in enumerate(keep)]
 
     # -- one-call block store (jfsx_store_batch) ---------------------------
     @staticmethod
