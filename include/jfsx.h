@@ -116,12 +116,14 @@ typedef struct jfsx_ctx jfsx_ctx;
 
 /* One 4 MiB-class block.  For JFSX_MEM_DEVICE batches src/dst must be
  * 16-byte aligned; dst may equal src (in place, as aead.Seal(p[:0]...) and
- * aead.Open(ciphertext[:0]...) are).  Length limits are the ciphers' own
- * (JFSX_EINVAL beyond them, where Go's Seal panics and Open fails):
- *   AES-256-GCM        len <= (2^32 - 2) * 16 B  (32-bit block counter from 2;
- *                      crypto/cipher gcm.go gcmMaxPlaintext)
- *   ChaCha20-Poly1305  len <= 2^38 - 64 B        (x/crypto v0.19.0
- *                      chacha20poly1305.go: block counter from 1)
+ * aead.Open(ciphertext[:0]...) are).  Length limits (JFSX_EINVAL beyond them):
+ *   AES-256-GCM        len <= (2^32 - 2) * 16 B  (the cipher's own: 32-bit
+ *                      block counter from 2; crypto/cipher gcm.go
+ *                      gcmMaxPlaintext, where Go's Seal panics and Open fails)
+ *   ChaCha20-Poly1305  len <= (2^32 - 1) * 16 B  (the engine's: it counts
+ *                      Poly1305 blocks in 32 bits; just under 64 GiB, below
+ *                      the cipher's 2^38 - 64 B of x/crypto v0.19.0
+ *                      chacha20poly1305.go)
  * Open with a failed tag (status JFSX_ETAG) releases nothing: dst is zeroed,
  * as Go's in-place aead.Open (encrypt.go:215) clears out on a mismatch, and a
  * plaintext CRC_GEN array is zeroed too. */

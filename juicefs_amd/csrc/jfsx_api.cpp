@@ -615,7 +615,10 @@ void order_largest_first(Task *t, size_t n, size_t max_units) {
 
 constexpr uint64_t kGcmMaxLen = (((uint64_t)1 << 32) - 2) * 16;
 constexpr uint64_t kGcmMinTask = 2 * (uint64_t)kSeg;  // 64 KiB
-constexpr uint64_t kCpMaxLen = ((uint64_t)1 << 38) - 64;
+// the cipher allows (2^32 - 1) * 64 B (x/crypto v0.19.0: (1<<38) - 64); the
+// kernels hold a slot's Poly1305 exponent, a count of 16-byte blocks, in 32
+// bits and 32 entries of r^(2^k) (cp_task's pexp, CpSched::r2k)
+constexpr uint64_t kCpMaxLen = (((uint64_t)1 << 32) - 1) * 16;
 
 // bytes per task of crc_segments_k: up to kCrcTaskBytes, but small enough that
 // a small batch still spreads over every CU (~2 tasks per CU), and a whole
@@ -681,8 +684,8 @@ int check_aead_args(int algo, int n, const jfsx_blk *blks, int crc_mode, bool de
         if (device && b.len && (!aligned16(b.src) || !aligned16(b.dst))) return JFSX_EINVAL;
         // the ciphers' own limits: GCM's 32-bit counter runs from 2, so past
         // (2^32 - 2) blocks it would wrap onto J0 (the tag mask) -- Go's Seal
-        // panics there (gcmMaxPlaintext); ChaCha20's 32-bit block counter runs
-        // from 1 (x/crypto v0.19.0: (1<<38) - 64)
+        // panics there (gcmMaxPlaintext); ChaCha20-Poly1305: the engine's own
+        // limit of 2^32 - 1 Poly1305 blocks, below the cipher's (kCpMaxLen)
         if (algo == JFSX_AES256GCM && b.len > kGcmMaxLen) return JFSX_EINVAL;
         if (algo == JFSX_CHACHA20P1305 && b.len > kCpMaxLen) return JFSX_EINVAL;
         if (crc_mode && !b.crc) return JFSX_EINVAL;
@@ -3733,6 +3736,9 @@ void jfsx_gen_key(uint64_t seed, uint64_t b, uint8_t key[32], uint8_t nonce[12])
 int jfsx_debug_plan(int kind, int n, const uint64_t *lens, uint64_t *task_bytes, uint64_t *ntasks, uint64_t *nslots,
                     uint64_t *tasks, uint64_t cap) {
     if (kind < kPlanGcm || kind > kPlanCrc || n < 0 || (n && !lens)) return JFSX_EINVAL;
+    // the per-algorithm length limits of the batch validation (check_aead_args)
+    for (int i = 0; i < n; i++)
+        if ((kind == kPlanGcm && lens[i] > kGcmMaxLen) || (kind == kPlanCp && lens[i] > kCpMaxLen)) return JFSX_EINVAL;
     const Plan p = plan_batch(kind, std::vector<uint64_t>(lens, lens + n));
     if (task_bytes) *task_bytes = p.task_bytes;
     if (ntasks) *ntasks = p.tasks.size();

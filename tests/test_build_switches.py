@@ -63,6 +63,7 @@ SWITCHES = {
     "JFSX_GF_HD": "jfsx_gf.h: function qualifiers",
     "JFSX_GF_BREAK": "jfsx_gf.h: scheduling fence hook",
     "JFSX_MD5_HD": "jfsx_md5.h: function qualifiers",
+    "JFSX_P5_HD": "jfsx_poly.h: function qualifiers",
     "JFSX_RSA_OPAQUE": "jfsx_rsa.h: value barrier hook",
     "JFSX_RSA_TRACE": "jfsx_rsa.h: operation trace hook of tests/harness/rsa_host.cpp",
 }

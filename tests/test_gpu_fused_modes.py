@@ -209,7 +209,7 @@ def test_device_open_in_place_tag_failure(eng, algo):
 def test_length_limits_refused_at_the_boundary(eng):
     fake = 1 << 40  # 16-B aligned, never dereferenced
     gcm_max = ((1 << 32) - 2) * 16
-    cp_max = (1 << 38) - 64
+    cp_max = ((1 << 32) - 1) * 16  # the engine's 32-bit count of Poly1305 blocks, below the cipher's 2^38 - 64
     for algo, ln in ((E.AES256GCM, gcm_max + 1), (E.AES256GCM, gcm_max + 16), (E.AES256GCM, 1 << 36),
                      (E.CHACHA20P1305, cp_max + 1), (E.CHACHA20P1305, 1 << 38)):
         for op in (eng.L.jfsx_seal_batch, eng.L.jfsx_open_batch):

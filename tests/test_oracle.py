@@ -58,6 +58,13 @@ def test_poly1305_rfc8439_2_5_2():
     assert orc.poly1305(key, b"Cryptographic Forum Research Group").hex() == "a8061dc1305136c6c22b8baf0c0127a9"
 
 
+@pytest.mark.parametrize("v", _load("poly1305_edges.json")["vectors"], ids=lambda v: v["name"])
+def test_poly1305_rfc8439_a3_edges(v):
+    """RFC 8439 A.3 #5-#11: the accumulator at p, below it by 5, wrapping 2^130
+    and h + s wrapping 2^128, on the oracle's 44/44/42-bit limbs."""
+    assert orc.poly1305(bytes.fromhex(v["key"]), bytes.fromhex(v["msg"])).hex() == v["tag"]
+
+
 def test_chacha20_block_rfc8439_2_3_2():
     key = bytes(range(32))
     nonce = bytes.fromhex("000000090000004a00000000")

@@ -118,6 +118,29 @@ def test_totals_from_2_gib(kind):
         assert check_plan(kind, lens) == top
 
 
+# the longest block each cipher's kernels take (jfsx.h, struct jfsx_blk): GCM's 32-bit counter runs from 2;
+# the ChaCha kernels count a block's 16-byte Poly1305 blocks in 32 bits
+MAX_LEN = {E.PLAN_GCM: ((1 << 32) - 2) * 16, E.PLAN_CHACHA: ((1 << 32) - 1) * 16}
+
+
+@pytest.mark.parametrize("kind", sorted(MAX_LEN), ids=lambda k: IDS[k])
+def test_length_limit_and_one_past_it(kind):
+    """The plan applies the batch validation's per-cipher limits: the longest
+    block plans (its last task's exponents fit the kernels' 32 bits), one byte
+    more is JFSX_EINVAL wherever it stands in the batch.  No buffer exists."""
+    top, limit = KINDS[kind][1], MAX_LEN[kind]
+    assert check_plan(kind, [limit]) == top
+    tasks = E.debug_plan(kind, [limit])[2]
+    assert max(c1 for _, _, c1 in tasks) == limit and -(-limit // 16) < 1 << 32
+    assert check_plan(kind, [5, limit, 0]) == top
+    for lens in ([limit + 1], [1, limit + 1], [limit + 1, 0], [limit + 16], [1 << 38], [(1 << 64) - 1]):
+        with pytest.raises(E.EngineError) as ei:
+            E.debug_plan(kind, lens)
+        assert ei.value.code == E.EINVAL, lens
+    # the CRC-only plan has no cipher's limit
+    assert E.debug_plan(E.PLAN_CRC, [limit + 1])[0] == KINDS[E.PLAN_CRC][1]
+
+
 @pytest.mark.parametrize("kind", sorted(KINDS), ids=lambda k: IDS[k])
 def test_seeded_random_batches(kind):
     rng = np.random.default_rng(20261019 + kind)
