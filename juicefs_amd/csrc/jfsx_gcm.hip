@@ -46,7 +46,8 @@ namespace jfsx {
 // is reached through the 16-bit ds_read offset: the CRC and GHASH bases
 // directly, the AES base as 0x10000 (bit 16 of the lane's v_perm operand loff)
 // plus the offset 24K.  So no table lookup spends a VALU op on its base; P,
-// above 128 KiB, is read once per row and pays one add for its base.
+// above 128 KiB, is read once per row and pays one add for its base in the
+// two-row body, one per four rows in the four-row period (gcm_task).
 // ---------------------------------------------------------------------------
 // plaintext in and ciphertext out as non-temporal block streams (coalesced
 // 1 KiB rows, read or written once): +0.7 % same box (profiles/r4/ab_gcm_rows.txt)
@@ -61,9 +62,11 @@ constexpr uint32_t kLdsBasis = kLdsAes + 65536;
 // shares (128 segments of 32 KiB per 4 MiB task) and a flag per segment
 constexpr uint32_t kLdsSegRaw = kLdsBasis + 2048;
 constexpr uint32_t kLdsSegFlag = kLdsSegRaw + 512;
-// P[c], c = the counter's low byte: round 2's four lookups on column 0, 16 B
+// P[c], c = the counter's low byte: round 2's four lookups on column 0, 16 B;
+// P[256], P[257] repeat P[0], P[1] for the four-row period, whose last row runs
+// two lanes past the low byte's wrap
 constexpr uint32_t kLdsP = kLdsSegFlag + 512;
-constexpr uint32_t kLdsBytes = kLdsP + 4096;
+constexpr uint32_t kLdsBytes = kLdsP + 4096 + 32;
 
 __device__ __forceinline__ uint32_t rotl8(uint32_t x) { return __builtin_amdgcn_alignbit(x, x, 24); }
 __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
@@ -167,9 +170,6 @@ __device__ __forceinline__ uint4 aes_r2_entry(const char *lds, uint32_t loff, ui
     return make_uint4(TA(a0, 0), rotl8(TB(a0, 3)), TB(a0, 2), rotl8(TA(a0, 1)));
 }
 
-// Keystream blocks of NS rows (the chains interleave for ILP) with rounds 1-2
-// taken from the task's table P and the lane's counter-uniform terms u;
-// ks comes out without the last round key (rk[56..59]).
 // side(AesStep<i>) runs after the i-th of the 12 round groups (rounds 1-2, then
 // 3 .. 13): the caller's place for work that fills the rounds' latency (the
 // CRC's L1 gathers); AesNoSide does nothing there.
@@ -181,24 +181,13 @@ struct AesNoSide {
     template <int I>
     __device__ __forceinline__ void operator()(AesStep<I>) const {}
 };
-template <int NS, class Side = AesNoSide>
-__device__ __forceinline__ void aes_ctr_blocks_u(const char *lds, uint32_t loff, const uint32_t *rk,
-                                                 const uint32_t *k1, const uint32_t (&ctr)[NS],
-                                                 const uint32_t (&u)[NS][4], const uint32_t (&du)[NS][4],
-                                                 const uint32_t (&cym)[NS], uint32_t (&ks)[NS][4],
-                                                 const Side &side = Side()) {
-    uint32_t a[NS][4], b[NS][4];
-    // u, du wave-uniform (SGPR operands); carry lanes (cym = ~0) add du = u(U) ^ u(U + 1)
-#define UC(t, w) (__builtin_amdgcn_bitop3_b32((t), cym[s], du[s][w], 0x78) ^ u[s][w]) /* t ^ (cym & du) ^ u */
-#pragma unroll
-    for (int s = 0; s < NS; s++) {
-        const uint4 pe = lds_u4(lds, ((ctr[s] << 4) & 0xff0u) + kLdsP);
-        b[s][0] = UC(pe.x, 0);
-        b[s][1] = UC(pe.y, 1);
-        b[s][2] = UC(pe.z, 2);
-        b[s][3] = UC(pe.w, 3);
-    }
-#undef UC
+// Rounds 3 .. 14 of NS rows (the chains interleave for ILP) from their round-2
+// states b, which are consumed; ks comes out without the last round key
+// (rk[56..59]).
+template <int NS, class Side>
+__device__ __forceinline__ void aes_rounds_3_14(const char *lds, uint32_t loff, const uint32_t *rk,
+                                                uint32_t (&b)[NS][4], uint32_t (&ks)[NS][4], const Side &side) {
+    uint32_t a[NS][4];
     side(AesStep<0>());
 #pragma unroll
     for (int s = 0; s < NS; s++) { AES_ROUND(a[s][0], a[s][1], a[s][2], a[s][3], b[s][0], b[s][1], b[s][2], b[s][3], 3); }
@@ -226,6 +215,51 @@ __device__ __forceinline__ void aes_ctr_blocks_u(const char *lds, uint32_t loff,
         AES_LAST(ks[s][2], a[s][2], a[s][3], a[s][0], a[s][1], 0u);
         AES_LAST(ks[s][3], a[s][3], a[s][0], a[s][1], a[s][2], 0u);
     }
+}
+
+// Keystream blocks of NS rows with rounds 1-2 taken from the task's table P
+// and the lane's counter-uniform terms u.
+template <int NS, class Side = AesNoSide>
+__device__ __forceinline__ void aes_ctr_blocks_u(const char *lds, uint32_t loff, const uint32_t *rk,
+                                                 const uint32_t *k1, const uint32_t (&ctr)[NS],
+                                                 const uint32_t (&u)[NS][4], const uint32_t (&du)[NS][4],
+                                                 const uint32_t (&cym)[NS], uint32_t (&ks)[NS][4],
+                                                 const Side &side = Side()) {
+    uint32_t b[NS][4];
+    // u, du wave-uniform (SGPR operands); carry lanes (cym = ~0) add du = u(U) ^ u(U + 1)
+#define UC(t, w) (__builtin_amdgcn_bitop3_b32((t), cym[s], du[s][w], 0x78) ^ u[s][w]) /* t ^ (cym & du) ^ u */
+#pragma unroll
+    for (int s = 0; s < NS; s++) {
+        const uint4 pe = lds_u4(lds, ((ctr[s] << 4) & 0xff0u) + kLdsP);
+        b[s][0] = UC(pe.x, 0);
+        b[s][1] = UC(pe.y, 1);
+        b[s][2] = UC(pe.z, 2);
+        b[s][3] = UC(pe.w, 3);
+    }
+#undef UC
+    aes_rounds_3_14<NS>(lds, loff, rk, b, ks, side);
+}
+
+// The same for rows Q, Q + 1 (Q = 0 or 2) of an aligned four-row period: the
+// period's first lane-0 counter has the low byte 2, so row q of the period
+// reads P at pb + 1024 q (pb = the lane's kLdsP + 16 (2 + lane); lanes 62-63
+// of row 3 reach the entries 256 and 257, copies of 0 and 1), every lane of
+// rows 0 .. 2 has the period's U, and in row 3 the lanes 62-63 (cy3 = ~0
+// there, else 0) have U + 1: du = u(U) ^ u(U + 1) is looked at for Q = 2 only.
+template <int Q, class Side>
+__device__ __forceinline__ void aes_ctr_blocks_p(const char *lds, uint32_t loff, const uint32_t *rk, uint32_t pb,
+                                                 const uint32_t (&u)[4], const uint32_t (&du)[4], uint32_t cy3,
+                                                 uint32_t (&ks)[2][4], const Side &side) {
+    uint32_t b[2][4];
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+        const uint4 pe = lds_u4(lds, pb + 1024u * (Q + s));
+        const uint32_t t[4] = {pe.x, pe.y, pe.z, pe.w};
+#pragma unroll
+        for (int w = 0; w < 4; w++)
+            b[s][w] = Q + s == 3 ? __builtin_amdgcn_bitop3_b32(t[w], cy3, du[w], 0x78) ^ u[w] : t[w] ^ u[w];
+    }
+    aes_rounds_3_14<2>(lds, loff, rk, b, ks, side);
 }
 
 // GHASH "multiply by H^64" with the byte-sliced table T[b][j] = (byte b at
@@ -518,7 +552,11 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
         // through the rows)
         uint32_t c = (wave << 6) | lane;
         asm volatile("" : "+v"(c));
-        reinterpret_cast<uint4 *>(lds + kLdsP)[c] = aes_r2_entry(lds, loff, sch->rk[3], sch->k1[0], c);
+        const uint4 e = aes_r2_entry(lds, loff, sch->rk[3], sch->k1[0], c);
+        reinterpret_cast<uint4 *>(lds + kLdsP)[c] = e;
+        if constexpr (!BS) {
+            if (c < 2) reinterpret_cast<uint4 *>(lds + kLdsP)[256 + c] = e;
+        }
     }
     __syncthreads();
     {
@@ -645,6 +683,8 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
     // the CRC's input is the loaded row itself: the plaintext in Seal, the
     // ciphertext (JFSX_CRC_CT) in Open
     constexpr bool kL1 = KL1 > 0 && kRowSplit && CRCMODE != 0 && OPEN == ((CRCMODE & 4) != 0);
+    // the 16-wave shape runs aligned runs of rows four at a time (below)
+    constexpr bool kPeriod = !BS;
     // the L1 path's row loop has no use for xl (its segment ends take xlB):
     // what follows the loop loads it where it is used, so it holds no
     // register through the rows
@@ -663,12 +703,17 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
         uint32_t uw0 = 0;
         bool uwok = false;
         // task row index of the stream's first row: a multiple of 2 (row
-        // pairs), so the compiler drops the segment-end test of the first row
-        // of a pair, which cannot end a segment
+        // pairs), so the first row of a pair cannot end a segment
         const uint32_t rb0 = (uint32_t)((ld0 - c0) >> 10) / 2u * 2u;
         // (the gathers read TT_4..15: the loop keeps the CRC state in B form)
         const CrcL1Base l1g = kL1 ? crc_l1_base(crc_composed(tab)) : CrcL1Base{0, 0};
-        for (; r0 + UR - 1 < rf; r0 += UR) {
+        // The two-row body: inlined at the four-row period's peel and in the loop
+        // of row pairs behind the periods, which stand in sequence.  (Nested,
+        // with one copy of the body, the two loops share live ranges and the
+        // body reloads scratch on every iteration: DESIGN 4.1, round 10.)
+        auto two_rows = [&]() __attribute__((always_inline)) {
+            // TWIN of the four-row period's half below (side
+            // steps and rows' tail): a change to either goes into both.
             uint4 dd[UR];
 #pragma unroll
             for (int u = 0; u < UR; u++) dd[u] = nn[u];
@@ -759,14 +804,135 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
                     st.A = crc_piece_b<kLdsTT>(lds, st.A, cq.x, crcL[u]);
                 else if (CRCMODE)
                     st.A = crc_piece<kLdsCrc>(lds, st.A, cq.x, cq.y, cq.z, cq.w);
-                if (CRCMODE && ((rb0 + (uint32_t)r0 + u) & 31) == 31) {
+                // (kPeriod: u == UR - 1 says what the four-row loop's steps of r0 hide from the compiler)
+                if (CRCMODE && (!kPeriod || u == UR - 1) && ((rb0 + (uint32_t)r0 + u) & 31) == 31) {
                     crc_segment_done<CRCMODE>(blk, tab, lane, kL1 ? crc_xlb(tab, lane) : xl, st.seg0,
                                               st.A, st.seg0 < st.sub0, lds, c0);
                     st.A = 0;
                     st.seg0 += kSeg;
                 }
             }
+        };
+        {
+            if constexpr (kPeriod) {
+                // Four rows per iteration from a row whose lane-0 counter has
+                // the low byte 2 (task rows = 0 mod 4: a task starts on a
+                // multiple of 64 KiB), so a stream that starts on a row
+                // = 2 mod 4 runs the two-row body once first, and the two or
+                // three rows that may be left take the loop of pairs below.  In
+                // such a period only row 3's lanes 62-63 carry into the
+                // counter's upper bits U, every row's P address is the lane's
+                // base plus a constant, only row 3 can end a segment, and rows
+                // 0-1 use one set of data registers (nn) while the other (mm)
+                // loads, rows 2-3 the other way round: no copies.
+                // (here r0 + 1 < rf: the enclosing test)
+                if ((((uint32_t)((ld0 + 1024 * r0) >> 4) + 2u) & 255u) != 2u) {
+                    two_rows();
+                    r0 += UR;
+                }
+                {
+                    for (; r0 + 3 < rf; r0 += 4) {
+                        const uint64_t o0 = ld0 + 1024 * r0 + lo;
+                        // rows Q, Q + 1 of the period from dd, the two rows after them into pf.
+                        // TWIN of the two-row body above (its side steps: gathers, folds and
+                        // prefetch; its rows' tail: XOR, store, GHASH, CRC step, segment end):
+                        // a change to the L1 schedule or the CRC step goes into both.  Kept
+                        // apart because either loop's register allocation follows its own form.
+                        auto half = [&](auto q, const uint4(&dd)[UR], uint4(&pf)[UR], const bool pre, const uint32_t pb,
+                                        const uint32_t(&up)[4], const uint32_t(&dp)[4],
+                                        const uint32_t cy3) __attribute__((always_inline)) {
+                            constexpr int Q = decltype(q)::value;
+                            if (!kL1 && pre) {
+#pragma unroll
+                                for (int u = 0; u < UR; u++) pf[u] = ald16<kAeadNt>(src + o0 + 1024 * (Q + UR + u));
+                            }
+                            constexpr int LG = kL1 ? JFSX_CRC_L1LG : 1, LLAG = JFSX_CRC_L1LAG,
+                                          LSTEPS = kL1 ? UR * KL1 / LG : 0;
+                            uint32_t crcL[UR], lv[LSTEPS ? LSTEPS : 1][LG];
+#pragma unroll
+                            for (int u = 0; u < UR; u++) crcL[u] = 0;
+                            auto side = [&](auto step) {
+                                if constexpr (kL1) {
+                                    constexpr int S = decltype(step)::value;
+                                    __builtin_amdgcn_sched_barrier(0);
+                                    if constexpr (S >= LLAG && S - LLAG < LSTEPS) {
+                                        constexpr int F = S - LLAG;
+                                        uint32_t t = crcL[F % UR];
+#pragma unroll
+                                        for (int j = 0; j + 1 < LG; j += 2) t = xor3(t, lv[F][j], lv[F][j + 1]);
+                                        if (LG & 1) t ^= lv[F][LG - 1];
+                                        crcL[F % UR] = t;
+                                    }
+                                    if constexpr (S < LSTEPS) {
+                                        crc_l1_issue<S, LG, UR>(l1g, dd, lv[S]);
+                                    } else if constexpr (S == LSTEPS) {
+                                        if (pre) {
+#pragma unroll
+                                            for (int u = 0; u < UR; u++)
+                                                pf[u] = ald16<kAeadNt>(src + o0 + 1024 * (Q + UR + u));
+                                        }
+                                    }
+                                    __builtin_amdgcn_sched_barrier(0);
+                                }
+                            };
+                            uint32_t ks2[UR][4];
+                            aes_ctr_blocks_p<Q>(lds, loff, rk, pb, up, dp, cy3, ks2, side);
+#pragma unroll
+                            for (int u = 0; u < UR; u++) {
+                                const uint64_t o = o0 + 1024 * (Q + u);
+                                const uint4 x =
+                                    make_uint4(xor3(dd[u].x, ks2[u][0], rk[56]), xor3(dd[u].y, ks2[u][1], rk[57]),
+                                               xor3(dd[u].z, ks2[u][2], rk[58]), xor3(dd[u].w, ks2[u][3], rk[59]));
+                                const uint4 c = OPEN ? dd[u] : x, p = OPEN ? x : dd[u];
+                                ast16<kAeadNt>(dst + o, OPEN ? p : c);
+                                const uint4 cq = crc_src<CRCMODE>(c, p);
+                                ghash_step(lds, st.acc, gl, c);
+                                if constexpr (kL1)
+                                    st.A = crc_piece_b<kLdsTT>(lds, st.A, cq.x, crcL[u]);
+                                else if (CRCMODE)
+                                    st.A = crc_piece<kLdsCrc>(lds, st.A, cq.x, cq.y, cq.z, cq.w);
+                                if (CRCMODE && Q + u == 3 && ((rb0 + (uint32_t)r0 + 3u) & 31) == 31) {
+                                    crc_segment_done<CRCMODE>(blk, tab, lane, kL1 ? crc_xlb(tab, lane) : xl, st.seg0,
+                                                              st.A, st.seg0 < st.sub0, lds, c0);
+                                    st.A = 0;
+                                    st.seg0 += kSeg;
+                                }
+                            }
+                            // the two rows end here: nothing of them sinks into the rows after them,
+                            // past the prefetch's branch, where it would hold their registers
+                            asm volatile("" : "+v"(st.A), "+v"(st.acc[0]), "+v"(st.acc[1]), "+v"(st.acc[2]), "+v"(st.acc[3]));
+                        };
+                        // the period's U and, for row 3's last two lanes, U + 1
+                        uint32_t U = (uint32_t)((ld0 + 1024 * r0) >> 12);
+                        OPAQUE(U);
+                        if (!uwok || U < uw0 || U + 1u - uw0 > 63u) {
+                            uw0 = U;
+                            aes_r2_uniform(lds, loff, rk, k1, uw0 + lane, uw);
+                            uwok = true;
+                        }
+                        const uint32_t i0 = U - uw0;
+                        uint32_t up[4], dp[4];
+#pragma unroll
+                        for (int k = 0; k < 4; k++) up[k] = __builtin_amdgcn_readlane(uw[k], i0);
+                        // the lane's P base and row 3's carry mask are made here, per period (the
+                        // empty asm keeps them from being hoisted): held through the task they
+                        // cost the two-row body two registers, which it pays in scratch
+                        uint32_t pl = lane;
+                        asm volatile("" : "+v"(pl));
+                        const uint32_t pb = (pl << 4) + (kLdsP + 32u);
+                        const uint32_t cy3 = pl >= 62u ? ~0u : 0u;
+                        uint4 mm[UR];
+                        half(AesStep<0>(), nn, mm, true, pb, up, up, 0u);
+#pragma unroll
+                        for (int k = 0; k < 4; k++) dp[k] = up[k] ^ __builtin_amdgcn_readlane(uw[k], i0 + 1);
+                        // (the pair after the period: the next period's rows 0-1 or the two-row body's)
+                        half(AesStep<2>(), mm, nn, r0 + 5 < rf, pb, up, dp, cy3);
+                    }
+                }
+            }
         }
+        // the rows in pairs (16-wave shape: the two or three rows left after the periods)
+        for (; r0 + UR - 1 < rf; r0 += UR) two_rows();
         if (r0 < rf) nxt = ald16<kAeadNt>(src + ld0 + 1024 * r0 + lo);
         // the loop ran, and its last row did not end a segment (A = 0 there)
         if constexpr (kL1) bform = ((rb0 + (uint32_t)r0) & 31) != 0;
