@@ -27,6 +27,8 @@
  *   jfsx_store_batch     uploadStagingFile's verified re-read +     pkg/chunk/cached_store.go:944-999, :371-413
  *                        upload's Compress + Encrypt + checksums,   (disk_cache.go:433-483, checksum.go:31-53)
  *                        one call
+ *   jfsx_store_objects   the same up to the stored object: the key  pkg/object/encrypt.go:164-194,
+ *                        wrap, header | C | tag, its checksum       checksum.go:31-53
  *   jfsx_rsa_oaep_decrypt_batch  rsaEncryptor.Decrypt, per read window  pkg/object/encrypt.go:132-134 (called :207-210)
  *   jfsx_rsa_oaep_encrypt_batch  rsaEncryptor.Encrypt, per upload window pkg/object/encrypt.go:128-130 (called :169)
  *   JFSX_AES256GCM /     NewDataEncryptor algo "aes256gcm-rsa" /    pkg/object/encrypt.go:142-162
@@ -710,7 +712,7 @@ int jfsx_store_batch(jfsx_ctx *ctx, int algo, int codec, int n, jfsx_sblk *blks,
  * lz4d_* / zstdd_* over the blocks that reached the decoder (rules 1-4 passed),
  * crc_* over the n pages with JFSX_CRC_GEN and, with JFSX_CRC_CT, over the n
  * images as jfsx_crc32c_segments would (crc_fail: rule 1). */
-#define JFSX_CODEC_NONE 0   /* jfsx_load_objects only: the volume has no --compress */
+#define JFSX_CODEC_NONE 0   /* jfsx_load_objects / jfsx_store_objects only: the volume has no --compress */
 #define JFSX_EKEY    7      /* per-block: "decryt key: crypto/rsa: decryption error" (encrypt.go:207-210),
                                or an unwrapped key that is not 32 bytes (NewCipher's key size error) */
 #define JFSX_EHEADER 8      /* per-block: "misformed ciphertext: %d %d" (encrypt.go:199-201) */
@@ -734,6 +736,69 @@ typedef struct jfsx_oblk {
 } jfsx_oblk;
 int jfsx_load_objects(jfsx_ctx *ctx, const jfsx_rsa_key *key, int algo, int codec, int n,
                       jfsx_oblk *blks, int crc_mode, int mem);
+
+/* One-call object store: the write side of jfsx_load_objects -- from the page
+ * to the stored object that store.put hands to the object store
+ * (dataEncryptor.Encrypt, pkg/object/encrypt.go:164-194):
+ *   BE16(256) | 12 | wrapped key (256) | nonce (12) | C | tag (16)
+ * for a batch of pages in one synchronous call: the page's verify or
+ * checksum(), rsaEncryptor.Encrypt of the data key (encrypt.go:169), Compress,
+ * Seal, the header and tag around C, and the object store's checksum of all of
+ * it (checksum.go:31-53).  The wrapped key and the tag never leave device
+ * memory on their own: the object comes down whole, and obj_crc is folded on
+ * the device.  The data key goes up once.
+ *   key, e    as jfsx_rsa_oaep_encrypt_batch: the key lives on ctx's device, e
+ *             is in Go's checkPub range
+ *   algo      JFSX_AES256GCM or JFSX_CHACHA20P1305 (without a cipher the object
+ *             is the image: jfsx_store_batch)
+ *   codec     JFSX_CODEC_NONE (C is the sealed page, img_len == len),
+ *             JFSX_CODEC_LZ4 or JFSX_CODEC_ZSTD
+ *   crc_mode  as jfsx_store_batch: NONE / GEN / VERIFY for the page, with
+ *             JFSX_CRC_CT OR'ed in or given alone for obj_crc
+ *   mem       JFSX_MEM_HOST: pageable or pinned memory at any alignment; only
+ *             obj[0, out_len) is written.  JFSX_MEM_DEVICE: (uintptr_t)obj % 16
+ *             == 1, so that C at obj + 271 is 16-byte aligned and the wrapped
+ *             key at obj + 3 and the nonce at obj + 259 are dword aligned; src
+ *             16-byte aligned when a page CRC or the Seal reads it (GEN /
+ *             VERIFY, or JFSX_CODEC_NONE); obj distinct from src; crc in device
+ *             memory
+ * JFSX_EINVAL before anything runs, with the records untouched: anything else,
+ * the limits of the separate calls, reserved != 0, obj_cap below
+ * jfsx_object_bound(codec, len), a NULL crc with GEN / VERIFY, a NULL key, a
+ * key of another device, e out of range.  The bytes are those of the separate
+ * calls: jfsx_rsa_oaep_encrypt_batch on key and seed, the compressor, then
+ * jfsx_seal_batch with key and nonce.  A page that fails JFSX_CRC_VERIFY gets
+ * JFSX_ECRC with crc_bad_seg / crc_got / crc_expect as jfsx_blk fills them and
+ * out_len, img_len and obj_crc 0; neither the compressor nor the cipher is
+ * started on its bytes, obj[0, obj_cap) is not written, and the other blocks
+ * are unaffected.  The call waits once with JFSX_CODEC_NONE unless the pages
+ * are verified, else twice, as jfsx_store_batch.  jfsx_metrics counts crc_*
+ * over the n pages (GEN / VERIFY), lz4c_* / zstdc_* and seal_* over the blocks
+ * that passed the verify (seal_bytes = the sum of img_len). */
+#define JFSX_OBJ_HDR_BYTES 271 /* BE16(256) | 12 | 256-byte wrapped key | 12-byte nonce */
+#define JFSX_OBJ_TAG_BYTES 16
+/* 271 + (len | jfsx_lz4_bound(len) | jfsx_zstd_bound(len)) + 16; 0 for an unknown codec */
+uint64_t jfsx_object_bound(int codec, uint64_t len);
+typedef struct jfsx_soblk {
+    uint8_t key[32];      /* data key: the caller's randomness (encrypt.go:165) */
+    uint8_t nonce[12];    /* encrypt.go:177                                     */
+    uint32_t reserved;    /* must be 0                                          */
+    uint8_t seed[32];     /* OAEP seed, as jfsx_rsa_oaep_encrypt_batch takes it */
+    const void *src;      /* the page                                           */
+    uint64_t len;
+    void *obj;            /* out: header | C | tag, contiguous                  */
+    uint64_t obj_cap;     /* >= jfsx_object_bound(codec, len)                   */
+    uint8_t *crc;         /* page CRCs. GEN: out, VERIFY: in; unused otherwise  */
+    uint64_t out_len;     /* out: bytes of the object, 0 for a failed block     */
+    uint64_t img_len;     /* out: bytes of C                                    */
+    uint32_t obj_crc;     /* out with JFSX_CRC_CT: CRC32C of obj[0, out_len)    */
+    int32_t status;       /* out: JFSX_OK / JFSX_ECRC                           */
+    int32_t crc_bad_seg;  /* out, as jfsx_sblk                                  */
+    uint32_t crc_got, crc_expect;
+    uint32_t reserved2;
+} jfsx_soblk;
+int jfsx_store_objects(jfsx_ctx *ctx, const jfsx_rsa_key *key, uint32_t e, int algo, int codec, int n,
+                       jfsx_soblk *blks, int crc_mode, int mem);
 
 /* header helper: returns wrapped-key length and offset/size of the nonce so a
  * caller can unwrap the key first (encrypt.go:197-205) */

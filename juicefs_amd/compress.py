@@ -521,3 +521,62 @@ def upload_blocks_fused(store, keys, blocks, compressor, enc=None, checksums=Tru
         objs.append(obj)
         crcs.append(crc)
     return (objs, crcs) if checksums else objs
+
+
+def upload_objects_fused(store, keys, blocks, compressor, enc, checksums=True, object_checksums=False):
+    """cachedStore.upload for a batch in one engine call that ends at the stored
+    object (jfsx_store_objects): the data keys' RSA-OAEP wrap, checksum() of
+    every block, Compress, Seal, the header and tag around C and the object
+    store's checksum run back to back on the device, and `store` receives what
+    comes down, as it is.  enc is the volume's DataEncryptor; compressor may be
+    the "none" compressor or None for a volume without --compress.
+
+    Key, OAEP seed and nonce of block i are drawn from enc's rand block by
+    block (DataEncryptor.draw_raw), the order DataEncryptor(wrap="gpu") draws
+    them in: with the same rand the objects are byte for byte those of
+    upload_blocks_fused with such an encryptor and, without a codec, those of
+    its EncryptBatch.  Returns (objects, crcs) with crcs[i] ==
+    checksum(blocks[i]), or the objects alone with checksums=False; with
+    object_checksums=True the decimal checksum strings of the objects
+    (checksum.go:31-53) follow as one more element.  An RSA key the engine does
+    not take goes through upload_blocks_fused / DataEncryptor.EncryptBatch."""
+    from .encrypt import rsa_public_exponent
+    coded = isinstance(compressor, (LZ4, ZStandard))
+    if enc is None:
+        raise ValueError("upload_objects_fused needs a DataEncryptor (a volume without one: upload_blocks_fused)")
+    codec = E.CODEC_NONE if not coded else E.CODEC_LZ4 if isinstance(compressor, LZ4) else E.CODEC_ZSTD
+    eng = compressor.eng if coded else enc.eng
+    blocks = [bytes(b) for b in blocks]
+    ke = enc.keyEncryptor
+    dk = ke._device_key(eng) if hasattr(ke, "_device_key") else None
+    e = rsa_public_exponent(ke.privKey) if dk is not None else 0
+    if dk is None or not 2 <= e <= 0x7FFFFFFF:
+        if coded:
+            res = upload_blocks_fused(store, keys, blocks, compressor, enc=enc, checksums=checksums)
+            objs = res[0] if checksums else res
+        else:
+            objs = enc.EncryptBatch(blocks)
+            for k, o in zip(keys, objs):
+                store.Put(k, o)
+            res = (objs, [eng.checksum(b) for b in blocks]) if checksums else objs
+        if not object_checksums:
+            return res
+        sums = [str(E.crc32c_update(0, o)) for o in objs]
+        return (res[0], res[1], sums) if checksums else (res, sums)
+    if not blocks:
+        out = ([], []) if checksums else []
+        return (out + ([],) if checksums else (out, [])) if object_checksums else out
+    items = [(key, seed, nonce, b) for b, (key, seed, nonce) in zip(blocks, enc.draw_raw(len(blocks)))]
+    res = eng.store_objects(dk, e, enc.algo, codec, items, crc=checksums, object_crc=object_checksums)
+    objs, crcs, sums = [], [], []
+    for k, (st, obj, crc, ocrc) in zip(keys, res):
+        if st != E.OK:  # no page CRCs were given to verify: the engine has no other per-block failure
+            raise CompressError("store %s: engine status %d" % (k, st))
+        store.Put(k, obj)
+        objs.append(obj)
+        crcs.append(crc)
+        sums.append(str(ocrc) if object_checksums else None)
+    out = (objs, crcs) if checksums else objs
+    if object_checksums:
+        return (objs, crcs, sums) if checksums else (objs, sums)
+    return out

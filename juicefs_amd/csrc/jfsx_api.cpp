@@ -455,6 +455,9 @@ struct jfsx_ctx {
     // store_h its pinned mirror (StoreBlk up, StoreRes down); store_stage the
     // pages of a host batch and the compressor's output slots; store_img the
     // packed images of a host batch (sized in phase B, from out_len).
+    // jfsx_store_objects (run_store_objects) runs on the same buffers: store_d /
+    // store_h also hold its SobjBlk | SobjRes in phase B, store_img the packed
+    // objects of a host batch, and rsa_d / rsa_h the wrap's workspace.
     Workspace store_crc, store_aead, store_ct;
     char *store_d = nullptr;
     size_t store_dcap = 0;
@@ -2165,6 +2168,8 @@ inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 struct StoreState {
     bool host = false, aead = false, ct = false, zstd = false;
+    bool plain = false;      // jfsx_store_objects with JFSX_CODEC_NONE: no compressor, the Seal reads the pages
+    size_t obj_extra = 0;    // jfsx_store_objects: bytes of an object's slot beyond its image (frame, alignment)
     int page_mode = 0;       // JFSX_CRC_NONE / GEN / VERIFY of the pages
     char *bounce = nullptr;  // pinned staging of the call's pageable pages (up) and images (down)
     size_t bcap = 0;
@@ -2184,10 +2189,13 @@ struct StoreState {
     size_t h_res = 0;            // offset of the downloaded StoreRes[n] in store_h
 };
 
-// Phase A: pages up, page CRCs, gate, compressor, verdicts down.
+// Phase A: pages up, page CRCs, gate, compressor, verdicts down.  st.plain:
+// pages up and the VERIFY stage alone (its BlkOut[n] comes down instead of the
+// verdicts); a GEN is left to the Seal's fused pass.
 int store_phase_a(jfsx_ctx *c, int n, const jfsx_sblk *blks, StoreState &st) {
     hipStream_t s = c->stream;
     const bool host = st.host;
+    const int page_mode = st.plain && st.page_mode == JFSX_CRC_GEN ? JFSX_CRC_NONE : st.page_mode;
     st.cap.assign(n, 0);
     st.poff.assign(n, 0);
     st.zoff.assign(n, 0);
@@ -2195,16 +2203,16 @@ int store_phase_a(jfsx_ctx *c, int n, const jfsx_sblk *blks, StoreState &st) {
     st.out_b.assign(n, 0);
     size_t page_bytes = 0, slot_bytes = 0, out_max = 0;
     for (int i = 0; i < n; i++) {
-        st.cap[i] = st.zstd ? zstd_bound(blks[i].len) : lz4_bound(blks[i].len);
+        st.cap[i] = st.plain ? blks[i].len : st.zstd ? zstd_bound(blks[i].len) : lz4_bound(blks[i].len);
         st.poff[i] = page_bytes;
         page_bytes += align256(blks[i].len);
         st.zoff[i] = slot_bytes;
         slot_bytes += align256(st.cap[i]);
-        out_max += align16(st.cap[i]);
+        out_max += align16(st.cap[i] + st.obj_extra);
     }
     st.page_bytes = page_bytes;
-    const bool use_slots = host || st.aead;  // else the compressor writes the callers' dst
-    st.cs = comp_setup(c, st.zstd, n);
+    const bool use_slots = !st.plain && (host || st.aead);  // else the compressor writes the callers' dst
+    if (!st.plain) st.cs = comp_setup(c, st.zstd, n);
     // device workspace of the store path
     size_t off = 0;
     const size_t o_sb = off; off = align256(off + sizeof(StoreBlk) * n);
@@ -2236,7 +2244,7 @@ int store_phase_a(jfsx_ctx *c, int n, const jfsx_sblk *blks, StoreState &st) {
                 st.all_in = st.all_in && st.in_b[i];
                 any_in = any_in || st.in_b[i];
             }
-            st.out_b[i] = !host_pinned(blks[i].dst, st.cap[i]);
+            st.out_b[i] = !host_pinned(blks[i].dst, st.cap[i] + st.obj_extra);
             st.all_out = st.all_out && st.out_b[i];
             any_out = any_out || st.out_b[i];
         }
@@ -2256,7 +2264,7 @@ int store_phase_a(jfsx_ctx *c, int n, const jfsx_sblk *blks, StoreState &st) {
     }
     // block records; the page CRC stage's blocks
     StoreBlk *hs = (StoreBlk *)(h + o_sb);
-    st.pb.assign(st.page_mode ? n : 0, jfsx_blk{});
+    st.pb.assign(page_mode ? n : 0, jfsx_blk{});
     for (int i = 0; i < n; i++) {
         const jfsx_sblk &b = blks[i];
         hs[i].src = !b.len ? nullptr : host ? (const uint8_t *)(stage + st.poff[i]) : (const uint8_t *)b.src;
@@ -2264,7 +2272,7 @@ int store_phase_a(jfsx_ctx *c, int n, const jfsx_sblk *blks, StoreState &st) {
         hs[i].sink = (uint8_t *)(d + o_sink + kStoreSink * (size_t)i);
         hs[i].len = b.len;
         hs[i].cap = st.cap[i];
-        if (st.page_mode) {
+        if (page_mode) {
             jfsx_blk &k = st.pb[i];
             memset(&k, 0, sizeof(k));
             k.src = hs[i].src;
@@ -2273,7 +2281,7 @@ int store_phase_a(jfsx_ctx *c, int n, const jfsx_sblk *blks, StoreState &st) {
         }
     }
     // 1. upload: the records, and every page once
-    HIP_OK(hipMemcpyAsync(d + o_sb, h + o_sb, sizeof(StoreBlk) * n, hipMemcpyHostToDevice, s));
+    if (!st.plain) HIP_OK(hipMemcpyAsync(d + o_sb, h + o_sb, sizeof(StoreBlk) * n, hipMemcpyHostToDevice, s));
     if (host) {
         if (st.all_in && page_bytes) {
             HIP_OK(hipMemcpyAsync(stage, st.bounce, page_bytes, hipMemcpyHostToDevice, s));
@@ -2287,12 +2295,13 @@ int store_phase_a(jfsx_ctx *c, int n, const jfsx_sblk *blks, StoreState &st) {
     }
     // 2. checksum() of every page, or its verify; the BlkOut[n] stays on the device
     const BlkOut *verified = nullptr;
-    if (st.page_mode) {
-        if ((rc = enqueue_crc(c, c->store_crc, s, c->store_ev[0], c->store_ev[1], n, st.pb.data(), st.page_mode,
-                              nullptr, nullptr, false, host)))
+    if (page_mode) {
+        if ((rc = enqueue_crc(c, c->store_crc, s, c->store_ev[0], c->store_ev[1], n, st.pb.data(), page_mode, nullptr,
+                              nullptr, st.plain, host)))
             return rc;
-        if (st.page_mode == JFSX_CRC_VERIFY) verified = (const BlkOut *)c->store_crc.dout;
+        if (page_mode == JFSX_CRC_VERIFY) verified = (const BlkOut *)c->store_crc.dout;
     }
+    if (st.plain) return 0;
     // 3. the gate, 4. the compressor: it sees a block only through the gate's descriptor
     const StoreBlk *ds = (const StoreBlk *)(d + o_sb);
     ZDev *dz = (ZDev *)(d + o_z);
@@ -4286,4 +4295,364 @@ extern "C" int jfsx_load_objects(jfsx_ctx *c, const jfsx_rsa_key *key, int algo,
     CtxScope es_(c);
     HIP_OK(hipSetDevice(c->device));
     return run_objects(c, key, algo, codec, n, blks, crc_mode, mem);
+}
+
+// ---------------------------------------------------------------------------
+// jfsx_store_objects: key wrap -> verify / checksum() -> compress -> Seal ->
+// header and tag -> object checksum of a batch of pages in one call
+// (dataEncryptor.Encrypt, encrypt.go:164-194; generateChecksum,
+// checksum.go:31-53).  jfsx_store_batch's chain (store_phase_a) with the wrap
+// in front, on the same stream and in the same grow-only buffers, and a phase
+// B of its own: the Seal writes C where the object has it, and sobj_frame_k
+// puts the header and the tag around it and folds obj_crc, so the host
+// assembles and folds nothing.  jfsx_objstore.hip has the order.
+// ---------------------------------------------------------------------------
+namespace {
+
+constexpr uint64_t kObjFrame = JFSX_OBJ_HDR_BYTES + JFSX_OBJ_TAG_BYTES;
+// a host batch's object in the packed device image and in the bounce buffer:
+// one byte into a 16-byte aligned slot, so that C is 16-byte aligned
+constexpr size_t kObjLead = 1;
+inline size_t obj_slot(uint64_t img_len) { return align16(kObjLead + kObjFrame + img_len); }
+
+uint64_t object_bound(int codec, uint64_t len) {
+    if (codec != JFSX_CODEC_NONE && codec != JFSX_CODEC_LZ4 && codec != JFSX_CODEC_ZSTD) return 0;
+    const uint64_t img = codec == JFSX_CODEC_ZSTD ? zstd_bound(len) : codec == JFSX_CODEC_LZ4 ? lz4_bound(len) : len;
+    if (codec == JFSX_CODEC_LZ4 && !img) return 0;  // past jfsx_lz4_bound's domain
+    return kObjFrame + img;
+}
+
+int check_sobj_args(const jfsx_rsa_key *key, uint32_t e, int algo, int codec, int n, const jfsx_soblk *blks,
+                    int crc_mode, int mem) {
+    if (algo != JFSX_AES256GCM && algo != JFSX_CHACHA20P1305) return JFSX_EINVAL;  // no cipher: jfsx_store_batch
+    if (codec != JFSX_CODEC_NONE && codec != JFSX_CODEC_LZ4 && codec != JFSX_CODEC_ZSTD) return JFSX_EINVAL;
+    if (crc_mode < 0 || (crc_mode & ~(3 | JFSX_CRC_CT)) || (crc_mode & 3) == 3) return JFSX_EINVAL;
+    if (mem != JFSX_MEM_DEVICE && mem != JFSX_MEM_HOST) return JFSX_EINVAL;
+    if (n < 0 || !key || e < jfsx_rsa::kMinE || e > jfsx_rsa::kMaxE) return JFSX_EINVAL;
+    const bool coded = codec != JFSX_CODEC_NONE, page_crc = (crc_mode & 3) != 0;
+    for (int i = 0; i < n; i++) {
+        const jfsx_soblk &b = blks[i];
+        if (b.reserved || b.reserved2) return JFSX_EINVAL;
+        if ((b.len && !b.src) || !b.obj) return JFSX_EINVAL;
+        if (coded && b.len > kLz4MaxInput) return JFSX_EINVAL;
+        const uint64_t img = codec == JFSX_CODEC_ZSTD ? zstd_bound(b.len) : coded ? lz4_bound(b.len) : b.len;
+        if (algo == JFSX_AES256GCM && img > kGcmMaxLen) return JFSX_EINVAL;
+        if (algo == JFSX_CHACHA20P1305 && img > kCpMaxLen) return JFSX_EINVAL;
+        if (b.obj_cap < kObjFrame + img) return JFSX_EINVAL;
+        if (page_crc && !b.crc) return JFSX_EINVAL;
+        if (mem == JFSX_MEM_DEVICE) {
+            if (((uintptr_t)b.obj & 15) != 1) return JFSX_EINVAL;
+            // the page CRC and, without a codec, the Seal read src where it lies
+            if ((page_crc || !coded) && b.len && !aligned16(b.src)) return JFSX_EINVAL;
+            if (b.obj == b.src) return JFSX_EINVAL;
+        }
+    }
+    return 0;
+}
+
+struct SobjState {
+    StoreState st;
+    std::vector<StoreRes> res;     // per block: what phase A found (wait #1), or OK / len without one
+    std::vector<size_t> seg_word;  // per sealed block: its first word in the Seal's CRC words
+    bool seal_pages = false;       // JFSX_CODEC_NONE with GEN: the Seal's fused pass writes the page CRCs
+    int seal_mult = 1;
+    size_t out_bytes = 0;
+    size_t o_msg = 0, o_ct = 0, msg_bytes = 0;  // the wrap's workspace
+    size_t h_sres = 0;                          // the downloaded SobjRes[m] in store_h
+};
+
+// The wrap, in jfsx_rsa_oaep_encrypt_batch's layout: msg | seed | len up in
+// one copy, the 256-byte results left at o_ct.
+int sobj_wrap(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t e, int n, const jfsx_soblk *blks, SobjState &so) {
+    constexpr size_t K = jfsx_rsa::kModBytes, S = kRsaWrapSlot, H = jfsx_rsa::kHash;
+    const size_t o_msg = 0, o_seed = align256(S * n), o_len = o_seed + align256(H * n),
+                 inbytes = o_len + align256(4 * (size_t)n), o_em = inbytes, o_ct = o_em + align256(K * n),
+                 dbytes = o_ct + align256(K * n);
+    int rc;
+    if ((rc = ensure_dev(c, &c->rsa_d, &c->rsa_dcap, dbytes))) return rc;
+    if ((rc = ensure_host(&c->rsa_h, &c->rsa_hcap, std::max(inbytes, K * n)))) return rc;
+    char *h = c->rsa_h, *d = c->rsa_d;
+    memset(h, 0, inbytes);
+    for (int i = 0; i < n; i++) {
+        memcpy(h + o_msg + S * i, blks[i].key, 32);
+        memcpy(h + o_seed + H * i, blks[i].seed, H);
+        ((uint32_t *)(h + o_len))[i] = 32;
+    }
+    so.o_msg = o_msg;
+    so.o_ct = o_ct;
+    so.msg_bytes = S * n;
+    HIP_OK(hipMemcpyAsync(d, h, inbytes, hipMemcpyHostToDevice, c->stream));
+    launch_begin();
+    launch_rsa_wrap(c->stream, key->d_key, e, n, (const uint8_t *)(d + o_msg), (const uint32_t *)(d + o_len),
+                    (const uint8_t *)(d + o_seed), (uint32_t *)(d + o_em), (uint8_t *)(d + o_ct));
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// Phase B: the Seal over the OK blocks into the objects (device memory) or the
+// packed device image (host memory), the frame, and every download.
+int sobj_phase_b(jfsx_ctx *c, int algo, int n, const jfsx_soblk *blks, SobjState &so) {
+    StoreState &st = so.st;
+    hipStream_t s = c->stream;
+    const bool host = st.host;
+    st.ooff.assign(n, 0);
+    size_t out_bytes = 0;
+    for (int i = 0; i < n; i++) {
+        if (so.res[i].status == jfsx_store::kBroken) return JFSX_EIO;
+        if (so.res[i].status != JFSX_OK) continue;
+        st.okidx.push_back(i);
+        st.ooff[i] = out_bytes;
+        out_bytes += obj_slot(so.res[i].out_len);
+    }
+    so.out_bytes = out_bytes;
+    const int m = (int)st.okidx.size();
+    if (!m) return 0;
+    so.seal_pages = st.plain && st.page_mode == JFSX_CRC_GEN;
+    const int seal_mode = so.seal_pages ? (st.ct ? (JFSX_CRC_GEN | JFSX_CRC_BOTH) : JFSX_CRC_GEN)
+                          : st.ct      ? (JFSX_CRC_GEN | JFSX_CRC_CT)
+                                       : JFSX_CRC_NONE;
+    so.seal_mult = so.seal_pages && st.ct ? 2 : 1;
+    // workspace: SobjBlk[m] up, SobjRes[m] down, behind phase A's records
+    const size_t o_sb = align256(st.h_res + sizeof(StoreRes) * n), o_res = align256(o_sb + sizeof(SobjBlk) * m),
+                 total = align256(o_res + sizeof(SobjRes) * m);
+    int rc;
+    if ((rc = ensure_host(&c->store_h, &c->store_hcap, total))) return rc;
+    if (host && (rc = ensure_dev(c, &c->store_img, &c->store_icap, out_bytes))) return rc;
+    // store_d is free again: phase A's kernels have finished (wait #1), or none of them ran
+    if ((rc = ensure_dev(c, &c->store_d, &c->store_dcap, total))) return rc;
+    so.h_sres = o_res;
+    SobjBlk *hb = (SobjBlk *)(c->store_h + o_sb);
+    st.sb.assign(m, jfsx_blk{});
+    so.seg_word.assign(m, 0);
+    static uint8_t crc_unused[8];  // never written: the CRC words stay in the Seal's workspace (host_crc)
+    size_t cw = 0;
+    for (int k = 0; k < m; k++) {
+        const int i = st.okidx[k];
+        const jfsx_soblk &b = blks[i];
+        const uint64_t img_len = so.res[i].out_len;
+        uint8_t *obj = host ? (uint8_t *)(c->store_img + st.ooff[i] + kObjLead) : (uint8_t *)b.obj;
+        jfsx_blk &a = st.sb[k];
+        memset(&a, 0, sizeof(a));
+        a.src = st.plain ? (!b.len ? nullptr : host ? (const void *)(c->store_stage + st.poff[i]) : b.src)
+                         : (const void *)(st.slots + st.zoff[i]);
+        a.dst = obj + JFSX_OBJ_HDR_BYTES;
+        a.len = img_len;
+        memcpy(a.nonce, b.nonce, 12);  // the key comes from the wrap's message slot (sobj_keys_k)
+        a.crc = seal_mode ? crc_unused : nullptr;
+        so.seg_word[k] = cw;
+        memset(&hb[k], 0, sizeof(SobjBlk));
+        hb[k].obj = obj;
+        hb[k].img_len = img_len;
+        memcpy(hb[k].nonce, b.nonce, 12);
+        hb[k].idx = (uint32_t)i;
+        hb[k].seg_off = (uint32_t)(cw + (so.seal_mult == 2 ? nseg_of(img_len) : 0));
+        cw += so.seal_mult * nseg_of(img_len);
+    }
+    char *d = c->store_d;
+    const SobjBlk *dsb = (const SobjBlk *)(d + o_sb);
+    HIP_OK(hipMemcpyAsync(d + o_sb, c->store_h + o_sb, sizeof(SobjBlk) * m, hipMemcpyHostToDevice, s));
+    const uint8_t *msg = (const uint8_t *)(c->rsa_d + so.o_msg);
+    const KeyHook hook = [&](hipStream_t ks, KeyIn *dk) { launch_sobj_keys(ks, m, dsb, msg, dk); };
+    if ((rc = enqueue_aead(c, c->store_aead, s, c->store_ev[2], c->store_ev[3], algo, false, m, st.sb.data(),
+                           seal_mode, nullptr, nullptr, false, nullptr, nullptr, seal_mode != 0, false, nullptr,
+                           nullptr, &hook)))
+        return rc;
+    Workspace &w = c->store_aead;
+    const uint8_t *words = (const uint8_t *)w.dout + w.crc_off;
+    launch_begin();
+    launch_sobj_frame(s, m, dsb, (const uint8_t *)(c->rsa_d + so.o_ct), (const BlkOut *)w.dout, st.ct ? words : nullptr,
+                      st.ct, c->tabs.crcx + 64, (SobjRes *)(d + o_res));
+    HIP_OK(hipGetLastError());
+    // the keys have reached the Seal's schedules: no copy stays in the wrap's workspace
+    HIP_OK(hipMemsetAsync(c->rsa_d + so.o_msg, 0, so.msg_bytes, s));
+    // downloads: the results, the page CRC words, the objects
+    HIP_OK(hipMemcpyAsync(c->store_h + o_res, d + o_res, sizeof(SobjRes) * m, hipMemcpyDeviceToHost, s));
+    if (st.page_mode && !st.plain) {
+        Workspace &pw = c->store_crc;
+        HIP_OK(hipMemcpyAsync(pw.h + pw.res_off, pw.dout, pw.down, hipMemcpyDeviceToHost, s));
+    }
+    if (so.seal_pages) {
+        if (host) {
+            HIP_OK(hipMemcpyAsync(w.h, w.dout, w.down, hipMemcpyDeviceToHost, s));
+        } else {
+            for (int k = 0; k < m; k++) {
+                const jfsx_soblk &b = blks[st.okidx[k]];
+                HIP_OK(hipMemcpyAsync(b.crc, words + 4 * so.seg_word[k], 4 * nseg_of(b.len), hipMemcpyDeviceToDevice,
+                                      s));
+            }
+        }
+    }
+    if (host) {
+        if (st.all_out) {
+            HIP_OK(hipMemcpyAsync(st.bounce, c->store_img, out_bytes, hipMemcpyDeviceToHost, s));
+        } else {
+            for (int i : st.okidx) {
+                const size_t at = st.ooff[i] + kObjLead;
+                HIP_OK(hipMemcpyAsync(st.out_b[i] ? st.bounce + at : (char *)blks[i].obj, c->store_img + at,
+                                      kObjFrame + so.res[i].out_len, hipMemcpyDeviceToHost, s));
+            }
+        }
+    }
+    return 0;
+}
+
+// Under c->mu for the whole call; the arguments have passed check_sobj_args and n > 0.
+int run_store_objects(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t e, int algo, int codec, int n, jfsx_soblk *blks,
+                      int crc_mode, int mem) {
+    int rc = 0;
+    SobjState so;
+    StoreState &st = so.st;
+    st.host = mem == JFSX_MEM_HOST;
+    st.aead = true;
+    st.ct = (crc_mode & JFSX_CRC_CT) != 0;
+    st.zstd = codec == JFSX_CODEC_ZSTD;
+    st.plain = codec == JFSX_CODEC_NONE;
+    st.page_mode = crc_mode & 3;
+    st.obj_extra = kObjLead + kObjFrame + 15;
+    auto wait = [&](const char *what) {
+        const hipError_t se = hipStreamSynchronize(c->stream);
+        if (!rc && se != hipSuccess) {
+            note_hip_error(se, __FILE__, __LINE__, what);
+            rc = JFSX_EIO;
+        }
+    };
+    // the blocks as store_phase_a takes them; dst is looked at (pinned or not), never written
+    std::vector<jfsx_sblk> sh(n);
+    for (int i = 0; i < n; i++) {
+        jfsx_sblk &b = sh[i];
+        memset(&b, 0, sizeof(b));
+        b.src = blks[i].src;
+        b.len = blks[i].len;
+        b.dst = blks[i].obj;
+        b.dst_cap = blks[i].obj_cap - kObjFrame;
+        b.crc = blks[i].crc;
+    }
+    const bool verify = st.page_mode == JFSX_CRC_VERIFY, wait1 = !st.plain || verify;
+    rc = sobj_wrap(c, key, e, n, blks, so);
+    if (!rc) rc = store_phase_a(c, n, sh.data(), st);
+    if (wait1 || rc) wait("hipStreamSynchronize(store_objects, wait #1)");
+    bool crc_done = false;  // the page CRC stage's results are in its mirror
+    if (!rc) {
+        so.res.assign(n, StoreRes{});
+        if (!st.plain) {
+            memcpy(so.res.data(), c->store_h + st.h_res, sizeof(StoreRes) * n);
+        } else {
+            if (verify) {
+                rc = finish_aead(c, c->store_crc, c->store_ev[0], c->store_ev[1], true, st.pb.data());
+                crc_done = true;
+            }
+            for (int i = 0; i < n && !rc; i++) {
+                StoreRes &r = so.res[i];
+                r.status = verify ? st.pb[i].status : JFSX_OK;
+                r.out_len = r.status == JFSX_OK ? blks[i].len : 0;
+                r.bad_seg = verify ? st.pb[i].crc_bad_seg : -1;
+                r.got = verify ? st.pb[i].crc_got : 0;
+                r.expect = verify ? st.pb[i].crc_expect : 0;
+            }
+        }
+    }
+    if (!rc) {
+        rc = sobj_phase_b(c, algo, n, blks, so);
+        wait("hipStreamSynchronize(store_objects, wait #2)");
+    }
+    // the page CRC stage (GEN with a codec: the CRC words to the callers' host
+    // arrays) and the Seal (JFSX_CODEC_NONE with GEN, host: the words of its fused pass)
+    if (!rc && st.page_mode && !st.plain) {
+        rc = finish_aead(c, c->store_crc, c->store_ev[0], c->store_ev[1], true, st.pb.data());
+        crc_done = true;
+    }
+    Workspace &w = c->store_aead;
+    if (!rc && w.n) {
+        if (w.timed && w.nt) {
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, c->store_ev[2], c->store_ev[3]) == hipSuccess) add_kernel_ms(c, ms);
+            else (void)hipGetLastError();
+        }
+        if (so.seal_pages && st.host) {
+            const char *hw = w.h + w.crc_off;
+            for (size_t k = 0; k < st.okidx.size(); k++) {
+                jfsx_soblk &b = blks[st.okidx[k]];
+                memcpy(b.crc, hw + 4 * so.seg_word[k], 4 * nseg_of(b.len));
+            }
+        }
+    }
+    for (Workspace *x : {&c->store_crc, &c->store_aead}) {
+        if (x == &c->store_crc && crc_done && !rc) continue;
+        x->n = 0;
+        x->nt = 0;
+        x->timed = false;
+        x->crc_back = false;
+    }
+    if (c->rsa_h) memset(c->rsa_h, 0, std::min(c->rsa_hcap, so.msg_bytes));  // the pinned copy of the data keys
+    if (!rc) {
+        const SobjRes *hr = (const SobjRes *)(c->store_h + so.h_sres);
+        std::vector<std::pair<char *, const char *>> cp;
+        std::vector<size_t> cl;
+        for (int i = 0; i < n; i++) {
+            jfsx_soblk &b = blks[i];
+            b.status = so.res[i].status;
+            b.crc_bad_seg = so.res[i].bad_seg;
+            b.crc_got = so.res[i].got;
+            b.crc_expect = so.res[i].expect;
+            b.out_len = b.img_len = 0;
+            b.obj_crc = 0;
+        }
+        for (size_t k = 0; k < st.okidx.size(); k++) {
+            const int i = st.okidx[k];
+            jfsx_soblk &b = blks[i];
+            b.status = hr[k].status;
+            b.out_len = hr[k].out_len;
+            b.img_len = hr[k].img_len;
+            b.obj_crc = hr[k].obj_crc;
+            if (st.host && st.out_b[i]) {
+                cp.push_back({(char *)b.obj, st.bounce + st.ooff[i] + kObjLead});
+                cl.push_back(b.out_len);
+                c->bounce.bytes_out += b.out_len;
+            }
+        }
+        par_copy(cp, cl);
+    }
+    if (st.bounce) bounce_put(c, st.bounce, st.bcap);
+    if (rc) return rc;
+    // jfsx_ctx_metrics: what the separate calls would have counted
+    std::lock_guard<std::mutex> g(c->stat_mu);
+    jfsx_metrics &mt = c->met;
+    uint64_t &c_blocks = st.zstd ? mt.zstdc_blocks : mt.lz4c_blocks, &c_in = st.zstd ? mt.zstdc_in : mt.lz4c_in;
+    uint64_t &c_out = st.zstd ? mt.zstdc_out : mt.lz4c_out;
+    if (st.page_mode) mt.crc_batches++;
+    if (!st.okidx.empty()) mt.seal_batches++;
+    for (int i = 0; i < n; i++) {
+        const jfsx_soblk &b = blks[i];
+        if (st.page_mode) {
+            mt.crc_ranges++;
+            mt.crc_bytes += b.len;
+            mt.crc_fail += b.status == JFSX_ECRC;
+        }
+        if (b.status != JFSX_OK) continue;
+        if (!st.plain) {
+            c_blocks++;
+            c_in += b.len;
+            c_out += b.img_len;
+        }
+        mt.seal_blocks++;
+        mt.seal_bytes += b.img_len;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" uint64_t jfsx_object_bound(int codec, uint64_t len) { return object_bound(codec, len); }
+
+extern "C" int jfsx_store_objects(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t e, int algo, int codec, int n,
+                                  jfsx_soblk *blks, int crc_mode, int mem) {
+    if (!c || (n > 0 && !blks)) return JFSX_EINVAL;
+    // argument errors before the context, the key or the device is touched
+    const int rc = check_sobj_args(key, e, algo, codec, n, blks, crc_mode, mem);
+    if (rc || n == 0) return rc;
+    if (key->device != c->device) return JFSX_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    CtxScope es_(c);
+    HIP_OK(hipSetDevice(c->device));
+    return run_store_objects(c, key, e, algo, codec, n, blks, crc_mode, mem);
 }

@@ -402,4 +402,29 @@ void launch_rsa_unwrap(hipStream_t s, const void *key, int n, const uint8_t *ct,
 constexpr int kRsaWrapSlot = 192;
 void launch_rsa_wrap(hipStream_t s, const void *key, uint32_t e, int n, const uint8_t *msg, const uint32_t *len,
                      const uint8_t *seed, uint32_t *em, uint8_t *ct);
+// One-call object store (jfsx_objstore.hip): the kernels that put the key wrap
+// in front of jfsx_store_batch's chain and the object's frame behind it.
+// SobjBlk describes one block that reached the Seal (the k-th of m); idx is its
+// place in the batch, where its key's message slot and wrapped key lie.
+struct SobjBlk {
+    uint8_t *obj;       // where the object starts, 1 mod 16 (device)
+    uint64_t img_len;   // bytes of C at obj + 271
+    uint32_t nonce[3];
+    uint32_t idx;
+    uint32_t seg_off;   // JFSX_CRC_CT: C's segment CRCs start at this word of the Seal's CRC words
+    uint32_t pad;
+};
+struct SobjRes {  // copied back to the host
+    uint64_t out_len, img_len;
+    uint32_t obj_crc;
+    int32_t status;
+};
+// one thread per block: the 32-byte data key out of slot idx of the wrap's
+// messages (kRsaWrapSlot bytes each) into keys[k].key
+void launch_sobj_keys(hipStream_t s, int m, const SobjBlk *sb, const uint8_t *msg, KeyIn *keys);
+// one wave per block: BE16(256) | 12 | wrapped[idx] | nonce at obj, the tag of
+// sealed[k] behind the image, and with crc_ct CRC32C of the whole object,
+// folded from the header, segs (big-endian segment CRCs) and the tag, into res[k]
+void launch_sobj_frame(hipStream_t s, int m, const SobjBlk *sb, const uint8_t *wrapped, const BlkOut *sealed,
+                       const uint8_t *segs, bool crc_ct, const uint32_t *x8pow, SobjRes *res);
 }  // namespace jfsx

@@ -399,6 +399,12 @@ class DataEncryptor:
                 raise w
         return [(k, w, nonce) for (k, _, nonce), w in zip(drawn, wrapped)]
 
+    def draw_raw(self, n):
+        """(key, OAEP seed, nonce) for n objects, drawn from rand object by
+        object in the order draw_keys uses with wrap="gpu"; nothing is wrapped
+        (jfsx_store_objects wraps on the device, in the same call as the Seal)."""
+        return [(self._rand(self.keyLen), self._rand(32), self._rand(12)) for _ in range(n)]
+
     def DecryptBatch(self, ciphertexts, checksums=None):
         """Returns, per object, the plaintext or the exception Decrypt would
         raise.  checksums (optional, one decimal string or None per object) are

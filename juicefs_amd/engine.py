@@ -29,7 +29,7 @@ EDSTSIZE = 5  # zstd: the output does not fit in dst_cap
 ESHORT = 6  # jfsx_load_batch: the image decoded to fewer bytes than the page ("read %s fully")
 CIPHER_NONE = -1  # jfsx_load_batch / jfsx_store_batch algo: the volume is not encrypted
 CODEC_LZ4, CODEC_ZSTD = 1, 2  # jfsx_load_batch / jfsx_store_batch codec
-CODEC_NONE = 0  # jfsx_load_objects only: the volume has no --compress
+CODEC_NONE = 0  # jfsx_load_objects / jfsx_store_objects only: the volume has no --compress
 EKEY = 7  # jfsx_load_objects: the data key does not unwrap, or is not 32 bytes long
 EHEADER = 8  # jfsx_load_objects: "misformed ciphertext" (the header does not describe itself)
 EINVAL, ENODEV, EIO, ENOMEM, EMISFORMED, EAGAIN = -22, -19, -5, -12, -74, -11
@@ -57,7 +57,7 @@ EXPORTS = [
     "jfsx_agg_data_encrypt", "jfsx_agg_data_decrypt",
     "jfsx_data_encrypt_ex", "jfsx_data_decrypt_ex", "jfsx_agg_data_encrypt_ex", "jfsx_agg_data_decrypt_ex",
     "jfsx_file_checksum_span", "jfsx_file_checksum_batch", "jfsx_file_checksum_fold",
-    "jfsx_load_batch", "jfsx_store_batch", "jfsx_load_objects",
+    "jfsx_load_batch", "jfsx_store_batch", "jfsx_load_objects", "jfsx_object_bound", "jfsx_store_objects",
 ]
 
 
@@ -141,6 +141,17 @@ class jfsx_oblk(ctypes.Structure):
         ("expect_crc", ctypes.c_uint32), ("obj_crc", ctypes.c_uint32), ("out_len", ctypes.c_uint64),
         ("status", ctypes.c_int32), ("codec_info", ctypes.c_int32), ("key_len", ctypes.c_int32),
         ("reserved2", ctypes.c_int32),
+    ]
+
+
+class jfsx_soblk(ctypes.Structure):
+    _fields_ = [
+        ("key", ctypes.c_uint8 * 32), ("nonce", ctypes.c_uint8 * 12), ("reserved", ctypes.c_uint32),
+        ("seed", ctypes.c_uint8 * 32), ("src", ctypes.c_void_p), ("len", ctypes.c_uint64),
+        ("obj", ctypes.c_void_p), ("obj_cap", ctypes.c_uint64), ("crc", ctypes.c_void_p),
+        ("out_len", ctypes.c_uint64), ("img_len", ctypes.c_uint64), ("obj_crc", ctypes.c_uint32),
+        ("status", ctypes.c_int32), ("crc_bad_seg", ctypes.c_int32), ("crc_got", ctypes.c_uint32),
+        ("crc_expect", ctypes.c_uint32), ("reserved2", ctypes.c_uint32),
     ]
 
 
@@ -266,6 +277,8 @@ def load_library(path=LIB_PATH):
             "jfsx_load_batch": (I, [P, I, I, I, ctypes.POINTER(jfsx_lblk), I, I]),
             "jfsx_store_batch": (I, [P, I, I, I, ctypes.POINTER(jfsx_sblk), I, I]),
             "jfsx_load_objects": (I, [P, P, I, I, I, ctypes.POINTER(jfsx_oblk), I, I]),
+            "jfsx_object_bound": (U64, [I, U64]),
+            "jfsx_store_objects": (I, [P, P, U32, I, I, I, ctypes.POINTER(jfsx_soblk), I, I]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -366,6 +379,15 @@ def lz4_bound(n):
 def zstd_bound(n):
     """ZSTD_compressBound (compress.go:80 CompressBound)."""
     return load_library().jfsx_zstd_bound(n)
+
+
+OBJ_HDR_BYTES = 271  # BE16(256) | 12 | wrapped key | nonce
+OBJ_TAG_BYTES = 16
+
+
+def object_bound(codec, n):
+    """Capacity jfsx_store_objects needs for the object of an n-byte page."""
+    return int(load_library().jfsx_object_bound(codec, n))
 
 
 def file_checksum_span(file_size, length, bytes_per_crc=512):
@@ -811,6 +833,64 @@ class Engine:
                  cbuf.tobytes() if (crc or verify is not None) else None,
                  arr[i].obj_crc if headers is not None else None)
                 for i, (_, dst, cbuf, _) in enumerate(keep)]
+
+    # -- one-call object store (jfsx_store_objects) ------------------------
+    @staticmethod
+    def make_soblocks(specs):
+        """specs: iterable of dicts with key, nonce, seed, src, len, obj,
+        obj_cap, [crc] (CRC_GEN / CRC_VERIFY); pointers as ints."""
+        specs = list(specs)
+        arr = (jfsx_soblk * max(len(specs), 1))()
+        for i, s in enumerate(specs):
+            b = arr[i]
+            ctypes.memmove(b.key, bytes(s["key"]), 32)
+            ctypes.memmove(b.nonce, bytes(s["nonce"]), 12)
+            ctypes.memmove(b.seed, bytes(s["seed"]), 32)
+            b.src, b.len = s.get("src"), s["len"]
+            b.obj, b.obj_cap = s.get("obj"), s["obj_cap"]
+            b.crc = s.get("crc")
+        return arr, len(specs)
+
+    def store_objects_batch(self, key, e, algo, codec, soblks, n, crc_mode=CRC_GEN, mem=MEM_DEVICE):
+        """The data-key wrap, the page's verify (or checksum()), Compress,
+        Seal, the object's header and tag and the object checksum of n pages in
+        one call.  key: rsa_key()'s handle, e: the public exponent.  Per-block
+        results in soblks[i].status (OK / ECRC), .out_len, .img_len, .obj_crc
+        and the crc_* fields; the object is obj[0, out_len)."""
+        self._check(self.L.jfsx_store_objects(self.ctx, key, e, algo, codec, n, soblks, crc_mode, mem),
+                    "jfsx_store_objects")
+
+    def store_objects(self, key, e, algo, codec, items, crc=True, verify=None, object_crc=True):
+        """Host bytes in, host bytes out.  items: (data key, seed, nonce, page)
+        per object.  crc: checksum() of every page comes back; verify: the
+        pages' CRC arrays to check instead; object_crc: the store's checksum of
+        every object.  Returns (status, object bytes, page crc bytes or None,
+        obj_crc or None) per item; self.store_info holds (img_len, crc_bad_seg,
+        crc_got, crc_expect) per item."""
+        specs, keep = [], []
+        for i, (dk, seed, nonce, page) in enumerate(items):
+            src = _u8(page)
+            cap = object_bound(codec, src.size)
+            obj = np.empty(cap, np.uint8)
+            if verify is not None:
+                cbuf = _u8(verify[i])
+            else:
+                cbuf = np.empty(4 * max(1, -(-int(src.size) // SEG)), np.uint8)
+            keep.append((src, obj, cbuf))
+            specs.append({"key": dk, "nonce": nonce, "seed": seed, "src": src.ctypes.data if src.size else None,
+                          "len": src.size, "obj": obj.ctypes.data, "obj_cap": cap,
+                          "crc": cbuf.ctypes.data if (crc or verify is not None) else None})
+        mode = CRC_VERIFY if verify is not None else CRC_GEN if crc else CRC_NONE
+        if object_crc:
+            mode |= CRC_CT
+        arr, cnt = self.make_soblocks(specs)
+        self.store_objects_batch(key, e, algo, codec, arr, cnt, mode, MEM_HOST)
+        self.store_info = [(arr[i].img_len, arr[i].crc_bad_seg, arr[i].crc_got, arr[i].crc_expect)
+                           for i in range(cnt)]
+        return [(arr[i].status, obj[:arr[i].out_len].tobytes(),
+                 cbuf.tobytes() if (crc or verify is not None) else None,
+                 arr[i].obj_crc if object_crc else None)
+                for i, (_, obj, cbuf) in enumerate(keep)]
 
     # -- asynchronous batches (jfsx_*_async + jfsx_wait) ------------------
     def _ticket(self, fn, what, *args):
