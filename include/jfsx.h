@@ -29,6 +29,9 @@
  *                        one call
  *   jfsx_store_objects   the same up to the stored object: the key  pkg/object/encrypt.go:164-194,
  *                        wrap, header | C | tag, its checksum       checksum.go:31-53
+ *   jfsx_compact_objects vfs.Compact: readSlice of the live ranges,  pkg/vfs/compact.go:54-109,
+ *                        zeros for holes, wSlice.upload of the new  pkg/chunk/cached_store.go:96-190
+ *                        slice; jfsx_compact_plan, jfsx_gather_batch
  *   jfsx_rsa_oaep_decrypt_batch  rsaEncryptor.Decrypt, per read window  pkg/object/encrypt.go:132-134 (called :207-210)
  *   jfsx_rsa_oaep_encrypt_batch  rsaEncryptor.Encrypt, per upload window pkg/object/encrypt.go:128-130 (called :169)
  *   JFSX_AES256GCM /     NewDataEncryptor algo "aes256gcm-rsa" /    pkg/object/encrypt.go:142-162
@@ -799,6 +802,123 @@ typedef struct jfsx_soblk {
 } jfsx_soblk;
 int jfsx_store_objects(jfsx_ctx *ctx, const jfsx_rsa_key *key, uint32_t e, int algo, int codec, int n,
                        jfsx_soblk *blks, int crc_mode, int mem);
+
+/* One-call slice compaction (vfs.Compact, pkg/vfs/compact.go:54-109): the live
+ * ranges of a chunk's old slices are read block by block (readSlice,
+ * rSlice.ReadAt, pkg/chunk/cached_store.go:96-190) and written, with zeros for
+ * holes (Id == 0), as one new slice that wSlice.upload cuts into blocks,
+ * compresses and encrypts.  Three entry points, from the inside out.
+ *
+ * jfsx_compact_plan -- host only, no device: from the slice list, in the order
+ * Compact receives it (meta.Slice, pkg/meta/interface.go:250-255), to the work.
+ *   srcs     one entry per distinct stored block that some slice reads, in
+ *            order of first use: indx = p / block_size, bsize = min(block_size,
+ *            size - indx * block_size) (rSlice.blockSize, cached_store.go:65-71);
+ *            the caller forms the key chunks/{id/1e6}/{id/1e3}/{id}_{indx}_{bsize}
+ *            (:73-78).  A block that two records of one id touch appears once.
+ *   pages    the new slice of sum(len) bytes cut into pages of block_size, the
+ *            last one shorter: its run of pieces, and page_len[j] its bytes
+ *   pieces   consecutive in their page; src indexes srcs, -1 means zeros.  A
+ *            piece crosses neither a source block nor a page boundary, and two
+ *            neighbours of one page that continue each other (the same source
+ *            at contiguous src_off, or both holes) are merged.
+ * Two-call sizing: n_src, n_page and n_piece are always written; when any
+ * capacity is too small the arrays stay untouched and the call returns
+ * JFSX_ENOMEM.  JFSX_ENOMEM with nothing written: a plan that cannot be held
+ * (a count beyond 2^31 - 1, as a tiny block_size under a total near 2^32
+ * gives, or memory for it that the host does not have).  JFSX_EINVAL: block_size == 0, n < 0, a NULL count, reserved !=
+ * 0, len == 0, off + len > size with id != 0, a total beyond 2^32 - 1. */
+#define JFSX_ESRC 9   /* per-page: a source block of the page did not load ("can't compact ... retry later",
+                         compact.go:83) */
+typedef struct jfsx_slice {
+    uint64_t id;          /* 0: a hole of len bytes */
+    uint32_t size, off, len;
+    uint32_t reserved;    /* must be 0 */
+} jfsx_slice;
+typedef struct jfsx_csrc {
+    uint64_t id;
+    uint32_t indx, bsize;
+} jfsx_csrc;
+typedef struct jfsx_cpage {
+    uint32_t piece_first, piece_count;
+    int32_t src_bad;      /* out of jfsx_compact_objects: the failed source of a JFSX_ESRC page, else -1 */
+    uint32_t reserved;    /* must be 0 */
+} jfsx_cpage;
+typedef struct jfsx_piece {
+    int32_t src;          /* index of the source, -1: zeros */
+    uint32_t reserved;    /* must be 0 */
+    uint64_t src_off;     /* ignored for a hole */
+    uint64_t len;         /* > 0 */
+} jfsx_piece;
+int jfsx_compact_plan(uint32_t block_size, int n, const jfsx_slice *slices, int src_cap, jfsx_csrc *srcs, int *n_src,
+                      int page_cap, jfsx_cpage *pages, uint64_t *page_len, int *n_page, int piece_cap,
+                      jfsx_piece *pieces, int *n_piece);
+
+/* jfsx_gather_batch -- the pages assembled by one kernel launch (gather_pages_k,
+ * jfsx_gather.hip).  Every byte of dst[j].data[0, len) is written exactly once:
+ * a data piece writes src[piece.src].data[src_off, src_off + len), a hole piece
+ * zeros; no memset runs in front and nothing outside a destination is written.
+ * Loads are confined to the naturally aligned 16-byte chunks that overlap a
+ * piece's source bytes.
+ *   JFSX_MEM_DEVICE  src[i].data and dst[j].data are 16-byte aligned; lengths,
+ *                    src_off and piece boundaries are arbitrary; no destination
+ *                    overlaps a source or another destination
+ *   JFSX_MEM_HOST    any alignment; staged as the other calls stage: pageable
+ *                    buffers through one pinned bounce buffer, packed, one
+ *                    copy up and one down; engine-pinned buffers where they lie
+ * JFSX_EINVAL before anything runs, with the records untouched: a piece index
+ * outside [-1, n_src), src_off + len > src.len, a piece of len 0, reserved !=
+ * 0, a sum of piece lengths that is not dst.len, a piece range outside
+ * n_piece, a NULL data with len > 0, a broken alignment or overlap rule.  A
+ * destination of len 0 without pieces writes nothing; two pieces may read the
+ * same source bytes. */
+typedef struct jfsx_gsrc {
+    const void *data;
+    uint64_t len;
+} jfsx_gsrc;
+typedef struct jfsx_gdst {
+    void *data;
+    uint64_t len;
+    uint32_t piece_first, piece_count;
+} jfsx_gdst;
+int jfsx_gather_batch(jfsx_ctx *ctx, int n_src, const jfsx_gsrc *src, int n_dst, jfsx_gdst *dst, int n_piece,
+                      const jfsx_piece *pieces, int mem);
+
+/* jfsx_compact_objects -- stored objects in, stored objects out, host memory on
+ * both sides; the pages live and die in device memory.  Under the context's
+ * lock, on its stream:
+ *   1 load    the images go up and jfsx_load_objects' chain runs into
+ *             engine-owned device pages; the call waits for the source verdicts
+ *   2 gate    a page is good when every source its pieces name came back
+ *             JFSX_OK with out_len == len.  Any other page gets JFSX_ESRC,
+ *             pages[j].src_bad = the source of its first piece that failed,
+ *             out_len, img_len and obj_crc 0; neither the compressor nor the
+ *             cipher nor the key wrap's result touches its bytes and obj[0,
+ *             obj_cap) is not written.  Good pages have src_bad = -1.
+ *   3 gather  one launch over the good pages
+ *   4 store   jfsx_store_objects' chain from the device pages into the engine's
+ *             packed objects, then out_len bytes per object come down
+ * src[i] is a jfsx_oblk as jfsx_load_objects takes it with JFSX_MEM_HOST (hdr,
+ * tag, src, src_len, expect_crc; len = the page length its key names) with dst
+ * and crc NULL; it gets status, out_len, codec_info, key_len and obj_crc as
+ * that call reports them.  dst[j] is a jfsx_soblk as jfsx_store_objects takes
+ * it (key, nonce, seed, obj, obj_cap, crc; len = the page length) with src
+ * NULL; it gets what that call reports.  The bytes are those of the separate
+ * calls with the same keys, nonces and seeds.
+ *   src_crc_mode  0 or JFSX_CRC_CT
+ *   dst_crc_mode  JFSX_CRC_NONE or JFSX_CRC_GEN, JFSX_CRC_CT optional
+ *   algo          JFSX_AES256GCM or JFSX_CHACHA20P1305
+ *   codec         JFSX_CODEC_NONE, JFSX_CODEC_LZ4 or JFSX_CODEC_ZSTD
+ * Argument errors (JFSX_EINVAL before the context or its device is touched, the
+ * records unchanged): those of the two calls for host memory, the gather's
+ * piece rules with src[i].len and dst[j].len as the lengths, pages[j].reserved
+ * != 0, a non-NULL dst / crc of a source or src of a destination.  Returns 0
+ * when blocks or pages failed.  jfsx_metrics counts what the separate calls
+ * count: jfsx_load_objects over the n_src sources and jfsx_store_objects over
+ * the good pages. */
+int jfsx_compact_objects(jfsx_ctx *ctx, const jfsx_rsa_key *key, uint32_t e, int algo, int codec, int n_src,
+                         jfsx_oblk *src, int src_crc_mode, int n_dst, jfsx_soblk *dst, jfsx_cpage *pages,
+                         int dst_crc_mode, int n_piece, const jfsx_piece *pieces);
 
 /* header helper: returns wrapped-key length and offset/size of the nonce so a
  * caller can unwrap the key first (encrypt.go:197-205) */

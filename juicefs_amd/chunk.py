@@ -6,6 +6,7 @@ the GPU engine.
   write_cache_file (flushPage's data||crc)    disk_cache.go:463-474
   openCacheFile(name, length, level)          disk_cache.go:1233-1253
   CacheFile.ReadAt(b, off)                    disk_cache.go:1255-1329
+  block_key(id, indx, bsize)                  cached_store.go:73-78
 
 The CRC32C work runs on the HIP engine (jfsx_checksum / jfsx_cache_verify).
 A mismatch raises ChecksumError("data checksum %d != expect %d").
@@ -23,6 +24,14 @@ csBlock = 32 << 10
 _LEVEL = {CsNone: 0, CsFull: 1, CsShrink: 2, CsExtend: 3}
 
 ChecksumError = E.ChecksumError
+
+
+def block_key(id, indx, bsize, hash_prefix=False):
+    """rSlice.key / wSlice.key (pkg/chunk/cached_store.go:73-78): the object key
+    of block indx of slice id, bsize its stored length."""
+    if hash_prefix:
+        return "chunks/%02X/%d/%d_%d_%d" % (id % 256, id // 1000 // 1000, id, indx, bsize)
+    return "chunks/%d/%d/%d_%d_%d" % (id // 1000 // 1000, id // 1000, id, indx, bsize)
 
 
 def checksum(data, eng=None):

@@ -580,3 +580,73 @@ def upload_objects_fused(store, keys, blocks, compressor, enc, checksums=True, o
     if object_checksums:
         return (objs, crcs, sums) if checksums else (objs, sums)
     return out
+
+
+def compact_fused(store, slices, new_id, block_size, compressor, enc, checksums=True, object_checksums=None):
+    """vfs.Compact (pkg/vfs/compact.go:54-109) for one chunk in one engine call
+    (jfsx_compact_objects): the live ranges of the old slices are read block by
+    block, written with zeros for holes as the new slice new_id, and that slice
+    is cut into blocks, compressed and sealed.  Stored objects go up and stored
+    objects come down; the pages exist in device memory only.
+
+    slices are (id, size, off, len) in the order Compact receives them
+    (meta.Slice), id 0 a hole.  The planner (jfsx_compact_plan) names the
+    source blocks, each is fetched once with store.Get(block_key(id, indx,
+    bsize)); object_checksums maps a source key to the decimal string the store
+    kept for it (a key it lacks is not verified).  Key, OAEP seed and nonce of
+    new block j are drawn from enc's rand block by block, as
+    upload_objects_fused draws them.  If every page comes back JFSX_OK the
+    objects are Put as block_key(new_id, j, len_j); if a Get fails or a page
+    does not, nothing is Put and CompressError names the failing source key and
+    its status (the reference's writer.Abort()).
+
+    Returns (keys, objects, crcs) with crcs[j] == checksum(page j), or (keys,
+    objects) with checksums=False; with object_checksums given, the decimal
+    checksum strings of the new objects follow as one more element."""
+    from .checksum import parse_checksum
+    from .chunk import block_key
+    from .encrypt import rsa_public_exponent
+    coded = isinstance(compressor, (LZ4, ZStandard))
+    if enc is None:
+        raise ValueError("compact_fused needs a DataEncryptor")
+    codec = E.CODEC_NONE if not coded else E.CODEC_LZ4 if isinstance(compressor, LZ4) else E.CODEC_ZSTD
+    eng = compressor.eng if coded else enc.eng
+    ke = enc.keyEncryptor
+    dk = ke._device_key(eng) if hasattr(ke, "_device_key") else None
+    e = rsa_public_exponent(ke.privKey) if dk is not None else 0
+    if dk is None or not 2 <= e <= 0x7FFFFFFF:
+        raise ValueError("compact_fused needs an RSA-2048 key with CRT parameters")
+    srcs, pages, pieces = E.compact_plan(block_size, slices)
+    skeys = [block_key(sid, indx, bsize) for sid, indx, bsize in srcs]
+    sources, expect = [], []
+    for k in skeys:
+        try:
+            o = bytes(store.Get(k, 0, -1))
+        except Exception as ex:
+            raise CompressError("compact %d: read %s: %s" % (new_id, k, ex))
+        klen, nlen = ((o[0] << 8) + o[1], o[2]) if len(o) >= 3 else (0, 0)
+        h = 3 + klen + nlen
+        if len(o) < 3 or len(o) < h + 16:  # too short to cut into header, C and tag (encrypt.go:199-201)
+            raise CompressError("compact %d: read %s: misformed ciphertext: %d %d" % (new_id, k, klen, nlen))
+        sources.append((o[:h], o[h:-16], o[-16:]))
+        w = parse_checksum(object_checksums.get(k)) if object_checksums is not None else None
+        expect.append(w if w is not None else (E.crc32c_update(0, o) if object_checksums is not None else None))
+    nkeys = [block_key(new_id, j, n) for j, (_, _, n) in enumerate(pages)]
+    if not pages:
+        out = ([], [], []) if checksums else ([], [])
+        return out + ([],) if object_checksums is not None else out
+    res = eng.compact_objects(dk, e, enc.algo, codec, sources, [b for _, _, b in srcs], enc.draw_raw(len(pages)),
+                              pages, pieces, crc=checksums, expect=expect if object_checksums is not None else None,
+                              object_crc=object_checksums is not None)
+    for (st, _, _, _, bad) in res:
+        if st == E.ESRC:
+            raise CompressError("compact %d: source %s: engine status %d" % (new_id, skeys[bad],
+                                                                             eng.compact_info[bad][0]))
+        if st != E.OK:
+            raise CompressError("compact %d: engine status %d" % (new_id, st))
+    for k, (_, obj, _, _, _) in zip(nkeys, res):
+        store.Put(k, obj)
+    out = (nkeys, [r[1] for r in res]) + (([r[2] for r in res],) if checksums else ())
+    if object_checksums is not None:
+        out += ([str(r[3]) for r in res],)
+    return out

@@ -19,7 +19,9 @@
 #include <functional>
 #include <map>
 #include <mutex>
+#include <new>
 #include <shared_mutex>
+#include <stdexcept>
 #include <thread>
 #include <vector>
 
@@ -30,6 +32,8 @@
 #include "jfsx_md5.h"
 #include "jfsx_store.h"
 #include "jfsx_objload.h"
+#include "jfsx_compact.h"
+#include "jfsx_gather.h"
 
 using namespace jfsx;
 
@@ -468,6 +472,19 @@ struct jfsx_ctx {
     char *store_img = nullptr;
     size_t store_icap = 0;
     hipEvent_t store_ev[6] = {};  // main-kernel timing of its three stages
+    // jfsx_gather_batch / jfsx_compact_objects: gat_d holds GPage | GPiece of a
+    // launch, gat_h its pinned mirror, gat_stage the sources and destinations
+    // of a host gather; cmp_d the images, source pages, new pages, packed
+    // objects and page CRC words of a compaction.  The load and store stages
+    // of a compaction run in the load_* / store_* buffers above.
+    char *gat_d = nullptr;
+    size_t gat_dcap = 0;
+    char *gat_h = nullptr;
+    size_t gat_hcap = 0;
+    char *gat_stage = nullptr;
+    size_t gat_scap = 0;
+    char *cmp_d = nullptr;
+    size_t cmp_dcap = 0;
     double ms_total = 0;
     uint64_t launches = 0;
     BouncePool bounce;       // pinned staging of pageable caller memory (host calls)
@@ -2725,6 +2742,10 @@ int jfsx_ctx_close(jfsx_ctx *c) {
     if (c->store_h) (void)hipHostFree(c->store_h);
     for (hipEvent_t e : c->store_ev)
         if (e) (void)hipEventDestroy(e);
+    if (c->gat_d) (void)hipFree(c->gat_d);
+    if (c->gat_stage) (void)hipFree(c->gat_stage);
+    if (c->cmp_d) (void)hipFree(c->cmp_d);
+    if (c->gat_h) (void)hipHostFree(c->gat_h);
     for (auto &kv : c->bounce.idle) {
         forget_pinned(kv.second);
         (void)hipHostFree(kv.second);
@@ -4360,6 +4381,8 @@ struct SobjState {
     size_t o_msg = 0, o_ct = 0, msg_bytes = 0;  // the wrap's workspace
     size_t h_sres = 0;                          // the downloaded SobjRes[m] in store_h
 };
+// jfsx_compact_objects: more downloads behind phase B's, in front of its wait
+using SobjTail = std::function<int(const SobjState &)>;
 
 // The wrap, in jfsx_rsa_oaep_encrypt_batch's layout: msg | seed | len up in
 // one copy, the 256-byte results left at o_ct.
@@ -4391,7 +4414,7 @@ int sobj_wrap(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t e, int n, const jfs
 
 // Phase B: the Seal over the OK blocks into the objects (device memory) or the
 // packed device image (host memory), the frame, and every download.
-int sobj_phase_b(jfsx_ctx *c, int algo, int n, const jfsx_soblk *blks, SobjState &so) {
+int sobj_phase_b(jfsx_ctx *c, int algo, int n, const jfsx_soblk *blks, SobjState &so, const SobjTail *tail) {
     StoreState &st = so.st;
     hipStream_t s = c->stream;
     const bool host = st.host;
@@ -4493,12 +4516,12 @@ int sobj_phase_b(jfsx_ctx *c, int algo, int n, const jfsx_soblk *blks, SobjState
             }
         }
     }
-    return 0;
+    return tail ? (*tail)(so) : 0;
 }
 
 // Under c->mu for the whole call; the arguments have passed check_sobj_args and n > 0.
 int run_store_objects(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t e, int algo, int codec, int n, jfsx_soblk *blks,
-                      int crc_mode, int mem) {
+                      int crc_mode, int mem, const SobjTail *tail = nullptr) {
     int rc = 0;
     SobjState so;
     StoreState &st = so.st;
@@ -4552,7 +4575,7 @@ int run_store_objects(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t e, int algo
         }
     }
     if (!rc) {
-        rc = sobj_phase_b(c, algo, n, blks, so);
+        rc = sobj_phase_b(c, algo, n, blks, so, tail);
         wait("hipStreamSynchronize(store_objects, wait #2)");
     }
     // the page CRC stage (GEN with a codec: the CRC words to the callers' host
@@ -4655,4 +4678,443 @@ extern "C" int jfsx_store_objects(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t
     CtxScope es_(c);
     HIP_OK(hipSetDevice(c->device));
     return run_store_objects(c, key, e, algo, codec, n, blks, crc_mode, mem);
+}
+
+// ---------------------------------------------------------------------------
+// Slice compaction (vfs.Compact, pkg/vfs/compact.go:54-109): jfsx_compact_plan
+// (jfsx_compact.h, host only), jfsx_gather_batch (gather_pages_k,
+// jfsx_gather.hip) and jfsx_compact_objects, which chains run_objects, the
+// gather and run_store_objects on the context's stream: stored objects in,
+// stored objects out, the pages in device memory only.
+// ---------------------------------------------------------------------------
+extern "C" int jfsx_compact_plan(uint32_t block_size, int n, const jfsx_slice *slices, int src_cap, jfsx_csrc *srcs,
+                                 int *n_src, int page_cap, jfsx_cpage *pages, uint64_t *page_len, int *n_page,
+                                 int piece_cap, jfsx_piece *pieces, int *n_piece) {
+    if (!n_src || !n_page || !n_piece || src_cap < 0 || page_cap < 0 || piece_cap < 0) return JFSX_EINVAL;
+    if ((src_cap && !srcs) || (page_cap && (!pages || !page_len)) || (piece_cap && !pieces)) return JFSX_EINVAL;
+    jfsx_compact::Plan p;
+    constexpr size_t kMax = 0x7FFFFFFF;
+    try {
+        const int rc = jfsx_compact::plan(block_size, n, slices, p);
+        if (rc) return rc;
+    } catch (const std::bad_alloc &) {
+        return JFSX_ENOMEM;  // nothing is thrown across the C ABI
+    } catch (const std::length_error &) {
+        return JFSX_ENOMEM;
+    }
+    if (p.srcs.size() > kMax || p.pages.size() > kMax || p.pieces.size() > kMax) return JFSX_ENOMEM;
+    *n_src = (int)p.srcs.size();
+    *n_page = (int)p.pages.size();
+    *n_piece = (int)p.pieces.size();
+    if (*n_src > src_cap || *n_page > page_cap || *n_piece > piece_cap) return JFSX_ENOMEM;
+    std::copy(p.srcs.begin(), p.srcs.end(), srcs);
+    std::copy(p.pages.begin(), p.pages.end(), pages);
+    std::copy(p.page_len.begin(), p.page_len.end(), page_len);
+    std::copy(p.pieces.begin(), p.pieces.end(), pieces);
+    return 0;
+}
+
+namespace {
+
+struct GatherRun {
+    uint32_t first, count;
+};
+
+// the piece rules of jfsx_gather_batch over n_src source lengths and n_dst
+// destinations (their lengths and piece runs)
+int check_pieces(int n_src, const uint64_t *slen, int n_dst, const uint64_t *dlen, const GatherRun *runs, int n_piece,
+                 const jfsx_piece *pieces) {
+    for (int k = 0; k < n_piece; k++) {
+        const jfsx_piece &p = pieces[k];
+        if (p.reserved || p.len == 0 || p.src < -1 || p.src >= n_src) return JFSX_EINVAL;
+        if (p.src >= 0 && (p.src_off > slen[p.src] || p.len > slen[p.src] - p.src_off)) return JFSX_EINVAL;
+    }
+    for (int j = 0; j < n_dst; j++) {
+        if ((uint64_t)runs[j].first + runs[j].count > (uint64_t)n_piece) return JFSX_EINVAL;
+        uint64_t sum = 0;
+        for (uint32_t k = 0; k < runs[j].count; k++) {
+            const uint64_t l = pieces[runs[j].first + k].len;
+            if (l > dlen[j] - sum) return JFSX_EINVAL;
+            sum += l;
+        }
+        if (sum != dlen[j]) return JFSX_EINVAL;
+    }
+    return 0;
+}
+
+// One gather launch on c->stream over the destinations with dp[j] != nullptr
+// and dlen[j] > 0; sp / dp are device addresses.  The pieces have passed
+// check_pieces.  timed: the launch lies between the events of the synchronous
+// paths (jfsx_ctx_set_timing).
+int gather_enqueue(jfsx_ctx *c, const uint8_t *const *sp, int n_dst, uint8_t *const *dp, const uint64_t *dlen,
+                   const GatherRun *runs, const jfsx_piece *pieces, bool timed, bool *launched = nullptr) {
+    using jfsx_gather::GPage;
+    using jfsx_gather::GPiece;
+    std::vector<GPage> pg;
+    std::vector<GPiece> pc;
+    uint64_t tiles = 0;
+    for (int j = 0; j < n_dst; j++) {
+        if (!dp[j] || !dlen[j]) continue;
+        GPage g{};
+        g.dst = dp[j];
+        g.len = dlen[j];
+        g.tile_first = tiles;
+        g.piece_first = (uint32_t)pc.size();
+        g.piece_count = runs[j].count;
+        uint64_t off = 0;
+        for (uint32_t k = 0; k < runs[j].count; k++) {
+            const jfsx_piece &p = pieces[runs[j].first + k];
+            pc.push_back(GPiece{p.src < 0 ? nullptr : sp[p.src] + p.src_off, off, p.len});
+            off += p.len;
+        }
+        tiles += jfsx_gather::tiles_of(dlen[j]);
+        pg.push_back(g);
+        if (pc.size() > 0xFFFFFFFFull) return JFSX_EINVAL;
+    }
+    if (pg.empty()) return 0;
+    const size_t o_pc = align256(sizeof(GPage) * pg.size()), total = o_pc + sizeof(GPiece) * pc.size();
+    int rc;
+    if ((rc = ensure_host(&c->gat_h, &c->gat_hcap, total))) return rc;
+    if ((rc = ensure_dev(c, &c->gat_d, &c->gat_dcap, total))) return rc;
+    memcpy(c->gat_h, pg.data(), sizeof(GPage) * pg.size());
+    memcpy(c->gat_h + o_pc, pc.data(), sizeof(GPiece) * pc.size());
+    HIP_OK(hipMemcpyAsync(c->gat_d, c->gat_h, total, hipMemcpyHostToDevice, c->stream));
+    if (timed) HIP_OK(hipEventRecord(c->ev_k0[0], c->stream));
+    launch_begin();
+    launch_gather(c->stream, c->ncu, (uint32_t)pg.size(), tiles, c->gat_d, c->gat_d + o_pc);
+    HIP_OK(hipGetLastError());
+    if (timed) HIP_OK(hipEventRecord(c->ev_k1[0], c->stream));
+    if (launched) *launched = true;
+    return 0;
+}
+
+// Under c->mu.  Host memory is staged as the other calls stage it
+// (objects_enqueue): gat_stage holds the sources and, behind them, the
+// destinations; pageable buffers go through one pinned bounce buffer, packed,
+// in one copy up and one copy down when all of a direction are pageable;
+// engine-pinned buffers are copied where they lie.
+int run_gather(jfsx_ctx *c, int n_src, const jfsx_gsrc *src, int n_dst, const jfsx_gdst *dst, const uint64_t *dlen,
+               const GatherRun *runs, const jfsx_piece *pieces, bool host) {
+    hipStream_t s = c->stream;
+    std::vector<const uint8_t *> sp(n_src, nullptr);
+    std::vector<uint8_t *> dp(n_dst, nullptr);
+    std::vector<size_t> soff(n_src), doff(n_dst);
+    std::vector<char> in_b(n_src, 0), out_b(n_dst, 0);
+    size_t src_bytes = 0, dst_bytes = 0, bcap = 0;
+    char *bounce = nullptr;
+    bool all_in = host, all_out = host, any_in = false, any_out = false;
+    int rc = 0;
+    if (host) {
+        for (int i = 0; i < n_src; i++) soff[i] = src_bytes, src_bytes += align256(src[i].len);
+        for (int j = 0; j < n_dst; j++) doff[j] = dst_bytes, dst_bytes += align256(dst[j].len);
+        if ((rc = ensure_dev(c, &c->gat_stage, &c->gat_scap, src_bytes + dst_bytes))) return rc;
+        for (int i = 0; i < n_src; i++) {
+            sp[i] = (const uint8_t *)c->gat_stage + soff[i];
+            if (!src[i].len) continue;
+            in_b[i] = !host_pinned(src[i].data, src[i].len);
+            all_in = all_in && in_b[i];
+            any_in = any_in || in_b[i];
+        }
+        for (int j = 0; j < n_dst; j++) {
+            dp[j] = (uint8_t *)c->gat_stage + src_bytes + doff[j];
+            if (!dst[j].len) continue;
+            out_b[j] = !host_pinned(dst[j].data, dst[j].len);
+            all_out = all_out && out_b[j];
+            any_out = any_out || out_b[j];
+        }
+        const size_t need = std::max(any_in ? src_bytes : 0, any_out ? dst_bytes : 0);
+        if (need && !(bounce = bounce_get(c, need, &bcap))) return JFSX_ENOMEM;
+        std::vector<std::pair<char *, const char *>> cp;
+        std::vector<size_t> cl;
+        for (int i = 0; i < n_src; i++)
+            if (in_b[i]) {
+                cp.push_back({bounce + soff[i], (const char *)src[i].data});
+                cl.push_back(src[i].len);
+                c->bounce.bytes_in += src[i].len;
+            }
+        par_copy(cp, cl);
+    }
+    // what is enqueued; the stream is waited for below whatever happens, so a failure does not return at once
+    const bool timed = c->timing;
+    bool launched = false;
+    const auto enqueue = [&]() {
+        if (host && all_in && src_bytes) {
+            HIP_OK(hipMemcpyAsync(c->gat_stage, bounce, src_bytes, hipMemcpyHostToDevice, s));
+        } else if (host) {
+            for (int i = 0; i < n_src; i++)
+                if (src[i].len)
+                    HIP_OK(hipMemcpyAsync((void *)sp[i], in_b[i] ? bounce + soff[i] : (const char *)src[i].data,
+                                          src[i].len, hipMemcpyHostToDevice, s));
+        } else {
+            for (int i = 0; i < n_src; i++) sp[i] = (const uint8_t *)src[i].data;
+            for (int j = 0; j < n_dst; j++) dp[j] = (uint8_t *)dst[j].data;
+        }
+        const int r = gather_enqueue(c, sp.data(), n_dst, dp.data(), dlen, runs, pieces, timed, &launched);
+        if (r) return r;
+        if (host && all_out && dst_bytes) {
+            HIP_OK(hipMemcpyAsync(bounce, c->gat_stage + src_bytes, dst_bytes, hipMemcpyDeviceToHost, s));
+        } else if (host) {
+            for (int j = 0; j < n_dst; j++)
+                if (dst[j].len)
+                    HIP_OK(hipMemcpyAsync(out_b[j] ? bounce + doff[j] : (char *)dst[j].data, dp[j], dst[j].len,
+                                          hipMemcpyDeviceToHost, s));
+        }
+        return 0;
+    };
+    rc = enqueue();
+    const hipError_t se = hipStreamSynchronize(s);
+    if (!rc && se != hipSuccess) {
+        note_hip_error(se, __FILE__, __LINE__, "hipStreamSynchronize(gather)");
+        rc = JFSX_EIO;
+    }
+    if (!rc && timed && launched) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, c->ev_k0[0], c->ev_k1[0]) == hipSuccess) add_kernel_ms(c, ms);
+        else (void)hipGetLastError();
+    }
+    if (!rc && host) {
+        std::vector<std::pair<char *, const char *>> cp;
+        std::vector<size_t> cl;
+        for (int j = 0; j < n_dst; j++)
+            if (out_b[j]) {
+                cp.push_back({(char *)dst[j].data, bounce + doff[j]});
+                cl.push_back(dst[j].len);
+                c->bounce.bytes_out += dst[j].len;
+            }
+        par_copy(cp, cl);
+    }
+    if (bounce) bounce_put(c, bounce, bcap);
+    return rc;
+}
+
+}  // namespace
+
+extern "C" int jfsx_gather_batch(jfsx_ctx *c, int n_src, const jfsx_gsrc *src, int n_dst, jfsx_gdst *dst, int n_piece,
+                                 const jfsx_piece *pieces, int mem) {
+    if (!c || n_src < 0 || n_dst < 0 || n_piece < 0) return JFSX_EINVAL;
+    if ((n_src && !src) || (n_dst && !dst) || (n_piece && !pieces)) return JFSX_EINVAL;
+    if (mem != JFSX_MEM_DEVICE && mem != JFSX_MEM_HOST) return JFSX_EINVAL;
+    // argument errors before the context or its device is touched
+    std::vector<uint64_t> slen(n_src), dlen(n_dst);
+    std::vector<GatherRun> runs(n_dst);
+    for (int i = 0; i < n_src; i++) {
+        if (src[i].len && !src[i].data) return JFSX_EINVAL;
+        slen[i] = src[i].len;
+    }
+    for (int j = 0; j < n_dst; j++) {
+        if (dst[j].len && !dst[j].data) return JFSX_EINVAL;
+        dlen[j] = dst[j].len;
+        runs[j] = GatherRun{dst[j].piece_first, dst[j].piece_count};
+    }
+    int rc = check_pieces(n_src, slen.data(), n_dst, dlen.data(), runs.data(), n_piece, pieces);
+    if (rc) return rc;
+    if (mem == JFSX_MEM_DEVICE) {
+        // 16-byte aligned, and no destination range overlaps a source's or another destination's
+        struct Iv {
+            uintptr_t lo, hi;
+            bool dst;
+        };
+        std::vector<Iv> iv;
+        for (int i = 0; i < n_src; i++) {
+            if (!src[i].len) continue;
+            if (!aligned16(src[i].data)) return JFSX_EINVAL;
+            iv.push_back(Iv{(uintptr_t)src[i].data, (uintptr_t)src[i].data + src[i].len, false});
+        }
+        for (int j = 0; j < n_dst; j++) {
+            if (!dst[j].len) continue;
+            if (!aligned16(dst[j].data)) return JFSX_EINVAL;
+            iv.push_back(Iv{(uintptr_t)dst[j].data, (uintptr_t)dst[j].data + dst[j].len, true});
+        }
+        std::sort(iv.begin(), iv.end(), [](const Iv &a, const Iv &b) { return a.lo < b.lo; });
+        uintptr_t end_any = 0, end_dst = 0;
+        for (const Iv &v : iv) {
+            if (v.lo < (v.dst ? end_any : end_dst)) return JFSX_EINVAL;
+            end_any = std::max(end_any, v.hi);
+            if (v.dst) end_dst = std::max(end_dst, v.hi);
+        }
+    }
+    if (n_dst == 0) return 0;
+    std::lock_guard<std::mutex> g(c->mu);
+    CtxScope es_(c);
+    HIP_OK(hipSetDevice(c->device));
+    return run_gather(c, n_src, src, n_dst, dst, dlen.data(), runs.data(), pieces, mem == JFSX_MEM_HOST);
+}
+
+namespace {
+
+// Under c->mu for the whole call; every argument has been checked.
+int run_compact(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t e, int algo, int codec, int n_src, jfsx_oblk *src,
+                int src_crc_mode, int n_dst, jfsx_soblk *dst, jfsx_cpage *pages, int dst_crc_mode,
+                const jfsx_piece *pieces) {
+    hipStream_t s = c->stream;
+    const bool gen = (dst_crc_mode & 3) == JFSX_CRC_GEN, ct_in = (src_crc_mode & JFSX_CRC_CT) != 0;
+    // cmp_d: images | source pages | new pages | objects (each 1 mod 16) | page CRC words
+    std::vector<size_t> ioff(n_src), soff(n_src), doff(n_dst), ooff(n_dst), coff(n_dst);
+    size_t off = 0;
+    for (int i = 0; i < n_src; i++) ioff[i] = off, off += align256(src[i].src_len);
+    const size_t img_bytes = off;
+    for (int i = 0; i < n_src; i++) soff[i] = off, off += align256(src[i].len);
+    for (int j = 0; j < n_dst; j++) doff[j] = off, off += align256(dst[j].len);
+    const size_t o_obj = off;
+    for (int j = 0; j < n_dst; j++) ooff[j] = off - o_obj, off += align256(kObjLead + object_bound(codec, dst[j].len));
+    const size_t obj_bytes = off - o_obj, o_crc = off;
+    for (int j = 0; j < n_dst; j++) coff[j] = off - o_crc, off += gen ? 4 * nseg_of(dst[j].len) : 0;
+    const size_t crc_bytes = off - o_crc;
+    int rc;
+    if ((rc = ensure_dev(c, &c->cmp_d, &c->cmp_dcap, off))) return rc;
+    char *d = c->cmp_d;
+    // one pinned buffer: the images on their way up, then the objects and CRC words on their way down
+    size_t bcap = 0;
+    char *bounce = bounce_get(c, std::max(img_bytes, align256(obj_bytes) + crc_bytes), &bcap);
+    if (!bounce) return JFSX_ENOMEM;
+    struct BounceHold {  // back to the pool on every way out; each of them has waited for the stream
+        jfsx_ctx *c;
+        char *p;
+        size_t cap;
+        ~BounceHold() { bounce_put(c, p, cap); }
+    } hold{c, bounce, bcap};
+    // 1. load: images up, jfsx_load_objects' chain in its device-memory form, wait
+    {
+        std::vector<std::pair<char *, const char *>> cp;
+        std::vector<size_t> cl;
+        for (int i = 0; i < n_src; i++)
+            if (src[i].src_len) {
+                cp.push_back({bounce + ioff[i], (const char *)src[i].src});
+                cl.push_back(src[i].src_len);
+                c->bounce.bytes_in += src[i].src_len;
+            }
+        par_copy(cp, cl);
+    }
+    if (img_bytes) HIP_OK(hipMemcpyAsync(d, bounce, img_bytes, hipMemcpyHostToDevice, s));
+    std::vector<jfsx_oblk> lo(src, src + n_src);
+    for (int i = 0; i < n_src; i++) {
+        lo[i].src = src[i].src_len ? d + ioff[i] : nullptr;
+        lo[i].dst = src[i].len ? d + soff[i] : nullptr;
+        lo[i].crc = nullptr;
+    }
+    // an all-hole chunk has no source: its pages are zeros from the gather alone
+    if (n_src && (rc = run_objects(c, key, algo, codec, n_src, lo.data(), src_crc_mode, JFSX_MEM_DEVICE))) return rc;
+    for (int i = 0; i < n_src; i++) {
+        src[i].status = lo[i].status;
+        src[i].out_len = lo[i].out_len;
+        src[i].codec_info = lo[i].codec_info;
+        src[i].key_len = lo[i].key_len;
+        if (ct_in) src[i].obj_crc = lo[i].obj_crc;
+    }
+    // 2. gate: a page is good when every source its pieces name is
+    std::vector<int> good;
+    for (int j = 0; j < n_dst; j++) {
+        int32_t bad = -1;
+        for (uint32_t k = 0; k < pages[j].piece_count && bad < 0; k++) {
+            const int32_t sidx = pieces[pages[j].piece_first + k].src;
+            if (sidx >= 0 && (src[sidx].status != JFSX_OK || src[sidx].out_len != src[sidx].len)) bad = sidx;
+        }
+        pages[j].src_bad = bad;
+        jfsx_soblk &b = dst[j];
+        b.status = bad < 0 ? JFSX_OK : JFSX_ESRC;
+        b.out_len = b.img_len = 0;
+        b.obj_crc = 0;
+        b.crc_bad_seg = -1;
+        b.crc_got = b.crc_expect = 0;
+        if (bad < 0) good.push_back(j);
+    }
+    const int m = (int)good.size();
+    if (!m) return 0;
+    // 3. gather: one launch over the good pages
+    std::vector<const uint8_t *> sp(n_src);
+    std::vector<uint8_t *> dp(n_dst, nullptr);
+    std::vector<uint64_t> dlen(n_dst);
+    std::vector<GatherRun> runs(n_dst);
+    for (int i = 0; i < n_src; i++) sp[i] = (const uint8_t *)d + soff[i];
+    for (int j = 0; j < n_dst; j++) {
+        dlen[j] = dst[j].len;
+        runs[j] = GatherRun{pages[j].piece_first, pages[j].piece_count};
+    }
+    for (int j : good) dp[j] = (uint8_t *)d + doff[j];
+    if ((rc = gather_enqueue(c, sp.data(), n_dst, dp.data(), dlen.data(), runs.data(), pieces, false))) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    // 4. store: jfsx_store_objects' chain in its device-memory form over the
+    // good pages; the objects and CRC words come down behind its phase B
+    std::vector<jfsx_soblk> so(m);
+    for (int k = 0; k < m; k++) {
+        const int j = good[k];
+        so[k] = dst[j];
+        so[k].src = dst[j].len ? d + doff[j] : nullptr;
+        so[k].obj = d + o_obj + ooff[j] + kObjLead;
+        so[k].obj_cap = object_bound(codec, dst[j].len);
+        so[k].crc = gen ? (uint8_t *)(d + o_crc + coff[j]) : nullptr;
+    }
+    const SobjTail tail = [&](const SobjState &ss) {
+        for (int k : ss.st.okidx) {
+            const size_t at = ooff[good[k]] + kObjLead;
+            HIP_OK(hipMemcpyAsync(bounce + at, d + o_obj + at, kObjFrame + ss.res[k].out_len, hipMemcpyDeviceToHost, s));
+        }
+        if (crc_bytes)
+            HIP_OK(hipMemcpyAsync(bounce + align256(obj_bytes), d + o_crc, crc_bytes, hipMemcpyDeviceToHost, s));
+        return 0;
+    };
+    if ((rc = run_store_objects(c, key, e, algo, codec, m, so.data(), dst_crc_mode, JFSX_MEM_DEVICE, &tail)))
+        return rc;
+    std::vector<std::pair<char *, const char *>> cp;
+    std::vector<size_t> cl;
+    for (int k = 0; k < m; k++) {
+        const int j = good[k];
+        jfsx_soblk &b = dst[j];
+        b.status = so[k].status;
+        b.out_len = so[k].out_len;
+        b.img_len = so[k].img_len;
+        b.obj_crc = so[k].obj_crc;
+        b.crc_bad_seg = so[k].crc_bad_seg;
+        b.crc_got = so[k].crc_got;
+        b.crc_expect = so[k].crc_expect;
+        if (b.status != JFSX_OK) continue;
+        cp.push_back({(char *)b.obj, bounce + ooff[j] + kObjLead});
+        cl.push_back(b.out_len);
+        c->bounce.bytes_out += b.out_len;
+        if (gen) memcpy(b.crc, bounce + align256(obj_bytes) + coff[j], 4 * nseg_of(b.len));
+    }
+    par_copy(cp, cl);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int jfsx_compact_objects(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t e, int algo, int codec, int n_src,
+                                    jfsx_oblk *src, int src_crc_mode, int n_dst, jfsx_soblk *dst, jfsx_cpage *pages,
+                                    int dst_crc_mode, int n_piece, const jfsx_piece *pieces) {
+    if (!c || n_src < 0 || n_dst < 0 || n_piece < 0) return JFSX_EINVAL;
+    if ((n_src && !src) || (n_dst && (!dst || !pages)) || (n_piece && !pieces)) return JFSX_EINVAL;
+    // argument errors before the context, the key or the device is touched:
+    // the two calls' rules for host memory on copies that carry a page address
+    if (algo != JFSX_AES256GCM && algo != JFSX_CHACHA20P1305) return JFSX_EINVAL;
+    if (src_crc_mode & ~JFSX_CRC_CT) return JFSX_EINVAL;
+    if (dst_crc_mode < 0 || (dst_crc_mode & 3) == JFSX_CRC_VERIFY) return JFSX_EINVAL;
+    static const uint8_t page_stub[16] = {};
+    std::vector<jfsx_oblk> lo(src, src + n_src);
+    std::vector<uint64_t> slen(n_src), dlen(n_dst);
+    for (int i = 0; i < n_src; i++) {
+        if (src[i].dst || src[i].crc) return JFSX_EINVAL;  // the page stays on the device
+        lo[i].dst = (void *)page_stub;
+        slen[i] = src[i].len;
+    }
+    int rc = check_objects_args(key, algo, codec, n_src, lo.data(), src_crc_mode, JFSX_MEM_HOST);
+    if (rc) return rc;
+    std::vector<jfsx_soblk> so(dst, dst + n_dst);
+    std::vector<GatherRun> runs(n_dst);
+    for (int j = 0; j < n_dst; j++) {
+        if (dst[j].src || pages[j].reserved) return JFSX_EINVAL;  // the page is assembled
+        so[j].src = page_stub;
+        dlen[j] = dst[j].len;
+        runs[j] = GatherRun{pages[j].piece_first, pages[j].piece_count};
+    }
+    if ((rc = check_sobj_args(key, e, algo, codec, n_dst, so.data(), dst_crc_mode, JFSX_MEM_HOST))) return rc;
+    if ((rc = check_pieces(n_src, slen.data(), n_dst, dlen.data(), runs.data(), n_piece, pieces))) return rc;
+    if (n_dst == 0) return 0;
+    if (key->device != c->device) return JFSX_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    CtxScope es_(c);
+    HIP_OK(hipSetDevice(c->device));
+    return run_compact(c, key, e, algo, codec, n_src, src, src_crc_mode, n_dst, dst, pages, dst_crc_mode, pieces);
 }

@@ -427,4 +427,8 @@ void launch_sobj_keys(hipStream_t s, int m, const SobjBlk *sb, const uint8_t *ms
 // folded from the header, segs (big-endian segment CRCs) and the tag, into res[k]
 void launch_sobj_frame(hipStream_t s, int m, const SobjBlk *sb, const uint8_t *wrapped, const BlkOut *sealed,
                        const uint8_t *segs, bool crc_ct, const uint32_t *x8pow, SobjRes *res);
+// jfsx_gather_batch (jfsx_gather.hip): one launch over the n_tiles tiles of
+// n_pages pages; pages / pieces are jfsx_gather::GPage[n_pages] and its GPiece
+// runs in device memory (jfsx_gather.h).  ncu sizes the grid: 8 workgroups per CU.
+void launch_gather(hipStream_t s, int ncu, uint32_t n_pages, uint64_t n_tiles, const void *pages, const void *pieces);
 }  // namespace jfsx

@@ -32,6 +32,8 @@ CODEC_LZ4, CODEC_ZSTD = 1, 2  # jfsx_load_batch / jfsx_store_batch codec
 CODEC_NONE = 0  # jfsx_load_objects / jfsx_store_objects only: the volume has no --compress
 EKEY = 7  # jfsx_load_objects: the data key does not unwrap, or is not 32 bytes long
 EHEADER = 8  # jfsx_load_objects: "misformed ciphertext" (the header does not describe itself)
+ESRC = 9  # jfsx_compact_objects: a source block of the page did not load ("can't compact ... retry later")
+GATHER_TILE = 16384  # jfsx_gather::kTile: bytes of a page one workgroup of gather_pages_k owns at a time
 EINVAL, ENODEV, EIO, ENOMEM, EMISFORMED, EAGAIN = -22, -19, -5, -12, -74, -11
 SEG = 32 << 10
 
@@ -58,6 +60,7 @@ EXPORTS = [
     "jfsx_data_encrypt_ex", "jfsx_data_decrypt_ex", "jfsx_agg_data_encrypt_ex", "jfsx_agg_data_decrypt_ex",
     "jfsx_file_checksum_span", "jfsx_file_checksum_batch", "jfsx_file_checksum_fold",
     "jfsx_load_batch", "jfsx_store_batch", "jfsx_load_objects", "jfsx_object_bound", "jfsx_store_objects",
+    "jfsx_compact_plan", "jfsx_gather_batch", "jfsx_compact_objects",
 ]
 
 
@@ -153,6 +156,34 @@ class jfsx_soblk(ctypes.Structure):
         ("status", ctypes.c_int32), ("crc_bad_seg", ctypes.c_int32), ("crc_got", ctypes.c_uint32),
         ("crc_expect", ctypes.c_uint32), ("reserved2", ctypes.c_uint32),
     ]
+
+
+class jfsx_slice(ctypes.Structure):
+    _fields_ = [("id", ctypes.c_uint64), ("size", ctypes.c_uint32), ("off", ctypes.c_uint32),
+                ("len", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class jfsx_csrc(ctypes.Structure):
+    _fields_ = [("id", ctypes.c_uint64), ("indx", ctypes.c_uint32), ("bsize", ctypes.c_uint32)]
+
+
+class jfsx_cpage(ctypes.Structure):
+    _fields_ = [("piece_first", ctypes.c_uint32), ("piece_count", ctypes.c_uint32), ("src_bad", ctypes.c_int32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class jfsx_piece(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_int32), ("reserved", ctypes.c_uint32), ("src_off", ctypes.c_uint64),
+                ("len", ctypes.c_uint64)]
+
+
+class jfsx_gsrc(ctypes.Structure):
+    _fields_ = [("data", ctypes.c_void_p), ("len", ctypes.c_uint64)]
+
+
+class jfsx_gdst(ctypes.Structure):
+    _fields_ = [("data", ctypes.c_void_p), ("len", ctypes.c_uint64), ("piece_first", ctypes.c_uint32),
+                ("piece_count", ctypes.c_uint32)]
 
 
 class jfsx_fsum(ctypes.Structure):
@@ -279,6 +310,14 @@ def load_library(path=LIB_PATH):
             "jfsx_load_objects": (I, [P, P, I, I, I, ctypes.POINTER(jfsx_oblk), I, I]),
             "jfsx_object_bound": (U64, [I, U64]),
             "jfsx_store_objects": (I, [P, P, U32, I, I, I, ctypes.POINTER(jfsx_soblk), I, I]),
+            "jfsx_compact_plan": (I, [U32, I, ctypes.POINTER(jfsx_slice), I, ctypes.POINTER(jfsx_csrc),
+                                      ctypes.POINTER(I), I, ctypes.POINTER(jfsx_cpage), ctypes.POINTER(U64),
+                                      ctypes.POINTER(I), I, ctypes.POINTER(jfsx_piece), ctypes.POINTER(I)]),
+            "jfsx_gather_batch": (I, [P, I, ctypes.POINTER(jfsx_gsrc), I, ctypes.POINTER(jfsx_gdst), I,
+                                      ctypes.POINTER(jfsx_piece), I]),
+            "jfsx_compact_objects": (I, [P, P, U32, I, I, I, ctypes.POINTER(jfsx_oblk), I, I,
+                                         ctypes.POINTER(jfsx_soblk), ctypes.POINTER(jfsx_cpage), I, I,
+                                         ctypes.POINTER(jfsx_piece)]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -388,6 +427,42 @@ OBJ_TAG_BYTES = 16
 def object_bound(codec, n):
     """Capacity jfsx_store_objects needs for the object of an n-byte page."""
     return int(load_library().jfsx_object_bound(codec, n))
+
+
+def make_pieces(pieces):
+    """pieces: (src, src_off, len) per piece, src -1 for zeros -> (jfsx_piece array, count)."""
+    pieces = list(pieces)
+    arr = (jfsx_piece * max(len(pieces), 1))()
+    for k, (src, src_off, ln) in enumerate(pieces):
+        arr[k].src, arr[k].src_off, arr[k].len = src, src_off, ln
+    return arr, len(pieces)
+
+
+def compact_plan(block_size, slices):
+    """jfsx_compact_plan, host only: slices are (id, size, off, len) in the order
+    vfs.Compact receives them, id 0 a hole.  Returns (sources, pages, pieces):
+    sources (id, indx, bsize) per distinct stored block in order of first use,
+    pages (piece_first, piece_count, page length) of the new slice cut at
+    block_size, pieces (src, src_off, len) with src -1 for zeros."""
+    L = load_library()
+    slices = list(slices)
+    sl = (jfsx_slice * max(len(slices), 1))()
+    for i, (sid, size, off, ln) in enumerate(slices):
+        sl[i].id, sl[i].size, sl[i].off, sl[i].len = sid, size, off, ln
+    ns, npg, npc = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    rc = L.jfsx_compact_plan(block_size, len(slices), sl, 0, None, ctypes.byref(ns), 0, None, None, ctypes.byref(npg),
+                             0, None, ctypes.byref(npc))
+    if rc not in (0, ENOMEM):
+        raise EngineError(rc, "jfsx_compact_plan")
+    srcs, pages = (jfsx_csrc * max(ns.value, 1))(), (jfsx_cpage * max(npg.value, 1))()
+    plen, pieces = (ctypes.c_uint64 * max(npg.value, 1))(), (jfsx_piece * max(npc.value, 1))()
+    rc = L.jfsx_compact_plan(block_size, len(slices), sl, ns.value, srcs, ctypes.byref(ns), npg.value, pages, plen,
+                             ctypes.byref(npg), npc.value, pieces, ctypes.byref(npc))
+    if rc:
+        raise EngineError(rc, "jfsx_compact_plan")
+    return ([(srcs[i].id, srcs[i].indx, srcs[i].bsize) for i in range(ns.value)],
+            [(pages[j].piece_first, pages[j].piece_count, plen[j]) for j in range(npg.value)],
+            [(pieces[k].src, pieces[k].src_off, pieces[k].len) for k in range(npc.value)])
 
 
 def file_checksum_span(file_size, length, bytes_per_crc=512):
@@ -891,6 +966,85 @@ class Engine:
                  cbuf.tobytes() if (crc or verify is not None) else None,
                  arr[i].obj_crc if object_crc else None)
                 for i, (_, obj, cbuf) in enumerate(keep)]
+
+    # -- slice compaction (jfsx_compact_plan / jfsx_gather_batch / jfsx_compact_objects)
+    compact_plan = staticmethod(compact_plan)
+
+    def gather_batch(self, n_src, gsrc, n_dst, gdst, n_piece, pieces, mem=MEM_DEVICE):
+        """One gather launch: every destination assembled from its run of
+        pieces (jfsx_gsrc / jfsx_gdst / jfsx_piece arrays)."""
+        self._check(self.L.jfsx_gather_batch(self.ctx, n_src, gsrc, n_dst, gdst, n_piece, pieces, mem),
+                    "jfsx_gather_batch")
+
+    def gather(self, sources, pages, pieces):
+        """Host bytes in, host bytes out.  sources: the source blocks; pages:
+        (piece_first, piece_count, page length) per page; pieces: (src, src_off,
+        len), src -1 for zeros -- as compact_plan returns them.  Returns the
+        pages."""
+        srcs = [_u8(b) for b in sources]
+        gs = (jfsx_gsrc * max(len(srcs), 1))()
+        for i, b in enumerate(srcs):
+            gs[i].data, gs[i].len = (b.ctypes.data if b.size else None), b.size
+        pages = list(pages)
+        outs = [np.empty(max(int(n), 1), np.uint8) for _, _, n in pages]
+        gd = (jfsx_gdst * max(len(pages), 1))()
+        for j, (first, count, n) in enumerate(pages):
+            gd[j].data, gd[j].len = (outs[j].ctypes.data if n else None), n
+            gd[j].piece_first, gd[j].piece_count = first, count
+        parr, cnt = make_pieces(pieces)
+        self.gather_batch(len(srcs), gs, len(pages), gd, cnt, parr, MEM_HOST)
+        return [o[:n].tobytes() for o, (_, _, n) in zip(outs, pages)]
+
+    def compact_objects_batch(self, key, e, algo, codec, n_src, oblks, src_crc_mode, n_dst, soblks, pages,
+                              dst_crc_mode, n_piece, pieces):
+        """Stored objects in, stored objects out: jfsx_load_objects' chain into
+        device pages, the gate, one gather launch and jfsx_store_objects' chain.
+        Per-source results in oblks[i] as load_objects_batch leaves them,
+        per-page results in soblks[j] as store_objects_batch leaves them (status
+        ESRC and pages[j].src_bad for a page whose source failed)."""
+        self._check(self.L.jfsx_compact_objects(self.ctx, key, e, algo, codec, n_src, oblks, src_crc_mode, n_dst,
+                                                soblks, pages, dst_crc_mode, n_piece, pieces), "jfsx_compact_objects")
+
+    def compact_objects(self, key, e, algo, codec, sources, lengths, draws, pages, pieces, crc=True, expect=None,
+                        object_crc=True):
+        """Host bytes in, host bytes out.  sources: (hdr, C, tag) per stored
+        source block with lengths[i] its page length; expect: the store's
+        checksum of each (asks for the verify); draws: (data key, seed, nonce)
+        per new page; pages / pieces as compact_plan returns them.  Returns
+        (status, object bytes, page crc bytes or None, obj_crc or None, src_bad)
+        per page; self.compact_info holds (status, out_len, codec_info, key_len,
+        obj_crc) per source and self.store_info (img_len,) per page."""
+        specs, keep = [], []
+        for i, ((hdr, img, tag), n) in enumerate(zip(sources, lengths)):
+            src, hbuf = _u8(img), _u8(hdr)
+            keep.append((src, hbuf))
+            specs.append({"hdr": hbuf.ctypes.data if hbuf.size else None, "hdr_len": hbuf.size, "tag": tag,
+                          "src": src.ctypes.data if src.size else None, "src_len": src.size, "dst": None,
+                          "len": int(n), "crc": None, "expect_crc": int(expect[i]) if expect is not None else 0})
+        oarr, n_src = self.make_oblocks(specs)
+        pages = list(pages)
+        sspecs, outs = [], []
+        for (dk, seed, nonce), (_, _, n) in zip(draws, pages):
+            cap = object_bound(codec, n)
+            obj = np.empty(cap, np.uint8)
+            cbuf = np.empty(4 * max(1, -(-int(n) // SEG)), np.uint8)
+            outs.append((obj, cbuf))
+            sspecs.append({"key": dk, "nonce": nonce, "seed": seed, "src": None, "len": int(n),
+                           "obj": obj.ctypes.data, "obj_cap": cap, "crc": cbuf.ctypes.data if crc else None})
+        sarr, n_dst = self.make_soblocks(sspecs)
+        cp = (jfsx_cpage * max(n_dst, 1))()
+        for j, (first, count, _) in enumerate(pages):
+            cp[j].piece_first, cp[j].piece_count, cp[j].src_bad = first, count, -1
+        parr, n_piece = make_pieces(pieces)
+        self.compact_objects_batch(key, e, algo, codec, n_src, oarr, CRC_CT if expect is not None else 0, n_dst, sarr,
+                                   cp, (CRC_GEN if crc else CRC_NONE) | (CRC_CT if object_crc else 0), n_piece, parr)
+        self.compact_info = [(oarr[i].status, oarr[i].out_len, oarr[i].codec_info, oarr[i].key_len, oarr[i].obj_crc)
+                             for i in range(n_src)]
+        self.store_info = [(sarr[j].img_len,) for j in range(n_dst)]
+        return [(sarr[j].status, obj[:sarr[j].out_len].tobytes(),
+                 cbuf.tobytes() if crc and sarr[j].status == OK else None,
+                 sarr[j].obj_crc if object_crc else None, cp[j].src_bad)
+                for j, (obj, cbuf) in enumerate(outs)]
 
     # -- asynchronous batches (jfsx_*_async + jfsx_wait) ------------------
     def _ticket(self, fn, what, *args):
