@@ -737,12 +737,50 @@ int check_aead_args(int algo, int n, const jfsx_blk *blks, int crc_mode, bool de
 // caller whose keys are already in device memory (the blocks' key fields are
 // then zero); null for everyone else.
 using KeyHook = std::function<void(hipStream_t, KeyIn *)>;
+
+// JFSX_KS_PHASES probe build (tools/taskedge_probe.py): where a device-resident
+// batch's step goes outside the main kernel.  Host steady_clock stamps through
+// enqueue_aead and run_aead, and events on the batch's stream around the
+// upload, keysetup, the main kernel, finalize and the copy-back;
+// jfsx_debug_edge_host reads them back.
+#ifdef JFSX_KS_PHASES
+struct EdgeHost {
+    // seconds: enqueue_aead entered, planned, descriptors filled, tasks
+    // dispatched, upload / keysetup / main / finalize and copy-back enqueued,
+    // stream idle, results copied out
+    double t[10] = {};
+    hipEvent_t ev[7] = {};  // upload <, >, keysetup >, main <, >, finalize >, copy-back >
+    bool have = false, ok = false;
+};
+EdgeHost g_edge;
+inline double edge_now() {
+    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+#define EDGE_T(i) (g_edge.t[i] = edge_now())
+#define EDGE_EV(i, st)                                       \
+    do {                                                     \
+        if (edge_on) (void)hipEventRecord(g_edge.ev[i], st); \
+    } while (0)
+#else
+#define EDGE_T(i) ((void)0)
+#define EDGE_EV(i, st) ((void)0)
+#endif
 int enqueue_aead(jfsx_ctx *c, Workspace &w, hipStream_t s, hipEvent_t k0, hipEvent_t k1, int algo, bool open, int n,
                  const jfsx_blk *blks, int crc_mode, hipStream_t up = nullptr, hipEvent_t up_ev = nullptr,
                  bool collect = true, hipStream_t fin = nullptr, hipEvent_t main_ev = nullptr,
                  bool host_crc = false, bool zc = false, hipStream_t ksst = nullptr, hipEvent_t ks_ev = nullptr,
                  const KeyHook *key_hook = nullptr) {
     const bool gcm = algo == JFSX_AES256GCM;
+#ifdef JFSX_KS_PHASES
+    // the plain device-resident call only: one stream, no pipeline
+    const bool edge_on = !up && !fin && !zc && !ksst && collect;
+    if (edge_on && !g_edge.have) {
+        g_edge.have = true;
+        for (hipEvent_t &e : g_edge.ev) (void)hipEventCreate(&e);
+    }
+    g_edge.ok = edge_on;
+    EDGE_T(0);
+#endif
     // JFSX_CRC_BOTH: the AEAD kernels checksum the plaintext (CRC_GEN) into the
     // first half of each CRC array and crc_segments_k checksums the ciphertext
     // in device memory into the second half -- before an in-place Open
@@ -765,6 +803,7 @@ int enqueue_aead(jfsx_ctx *c, Workspace &w, hipStream_t s, hipEvent_t k0, hipEve
     const uint32_t slots = gcm ? kSlotsPerTask : kCpWaves;
     const Plan plan = plan_batch(gcm ? kPlanGcm : kPlanCp, lens);
     const size_t nt = plan.tasks.size();
+    EDGE_T(1);
     // device workspace layout
     size_t off = 0;
     const size_t o_keys = off; off = align256(off + sizeof(KeyIn) * n);
@@ -827,6 +866,7 @@ int enqueue_aead(jfsx_ctx *c, Workspace &w, hipStream_t s, hipEvent_t k0, hipEve
         hb[i].tag_in = open ? (const uint8_t *)(d + o_tagin + 16 * (size_t)i) : nullptr;
         memcpy(h + o_tagin + 16 * (size_t)i, b.tag, 16);
     }
+    EDGE_T(2);
     uint32_t max_slots = 0;
     for (size_t t = 0; t < nt; t++) {
         BlkDev &bd = hb[plan.tasks[t].blk];
@@ -836,6 +876,7 @@ int enqueue_aead(jfsx_ctx *c, Workspace &w, hipStream_t s, hipEvent_t k0, hipEve
     }
     plan.dispatch((Task *)(h + o_task));
     cplan.dispatch((Task *)(h + o_ctask));
+    EDGE_T(3);
     // the ciphertext pass of BOTH on stream st
     auto ct_pass = [&](hipStream_t st) {
         launch_crc_segments(st, (int)ctasks.size(), (const Task *)(d + o_ctask), (const BlkDev *)(d + o_cblk), c->tabs);
@@ -858,7 +899,10 @@ int enqueue_aead(jfsx_ctx *c, Workspace &w, hipStream_t s, hipEvent_t k0, hipEve
         // the blocks' data
         launch_pull(kss ? ksst : s, d, h, h_bytes);
     } else {
+        EDGE_EV(0, s);
         HIP_OK(hipMemcpyAsync(d, h, h_bytes, hipMemcpyHostToDevice, up ? up : s));
+        EDGE_EV(1, s);
+        EDGE_T(4);
     }
     // the compute stream waits for the upload before the first kernel that
     // reads what it carries: keysetup when the descriptors ride it, else main
@@ -869,6 +913,8 @@ int enqueue_aead(jfsx_ctx *c, Workspace &w, hipStream_t s, hipEvent_t k0, hipEve
     if (key_hook) (*key_hook)(ks, (KeyIn *)(d + o_keys));
     if (gcm) launch_gcm_keysetup(ks, n, dk, db, (GcmSched *)(d + o_sched), c->tabs, c->bitslice);
     else launch_cp_keysetup(ks, n, dk, db, (CpSched *)(d + o_sched));
+    EDGE_EV(2, s);
+    EDGE_T(5);
     if (kss) {  // the descriptors and schedules are ready for the compute stream
         HIP_OK(hipEventRecord(ks_ev, ksst));
         HIP_OK(hipStreamWaitEvent(s, ks_ev, 0));
@@ -882,12 +928,15 @@ int enqueue_aead(jfsx_ctx *c, Workspace &w, hipStream_t s, hipEvent_t k0, hipEve
             if (blks[i].len == 0) HIP_OK(hipMemsetAsync(hb[i].crc, 0, 4 * mult, s));
     if (both && open) ct_pass(s);
     if (c->timing) HIP_OK(hipEventRecord(k0, s));
+    EDGE_EV(3, s);
     if (gcm)
         launch_gcm_main(s, (int)nt, c->ncu, dq, open, crc_mode, c->bitslice, dt, db, (const GcmSched *)(d + o_sched),
                         dpart, dpexp, c->tabs, c->crc_l1);
     else
         launch_cp_main(s, (int)nt, c->ncu, dq, open, crc_mode, dt, db, (const CpSched *)(d + o_sched), dpart, dpexp,
                        c->tabs);
+    EDGE_EV(4, s);
+    EDGE_T(6);
     if (c->timing) HIP_OK(hipEventRecord(k1, s));
     if (both && !open) ct_pass(s);
     if (fin) {
@@ -905,7 +954,10 @@ int enqueue_aead(jfsx_ctx *c, Workspace &w, hipStream_t s, hipEvent_t k0, hipEve
     w.crc_back = hc_out;
     w.crc_mult = mult;
     w.res_off = o_hres;
+    EDGE_EV(5, s);
     if (collect && !zc) HIP_OK(hipMemcpyAsync(h, dout, down, hipMemcpyDeviceToHost, fs));
+    EDGE_EV(6, s);
+    EDGE_T(7);
     w.n = n;
     w.nt = nt;
     w.timed = c->timing;
@@ -978,7 +1030,9 @@ int run_aead(jfsx_ctx *c, int algo, bool open, int n, jfsx_blk *blks, int crc_mo
         return rc;
     }
     HIP_OK(hipStreamSynchronize(c->stream));
+    EDGE_T(8);
     if ((rc = finish_aead(c, c->ws[0], c->ev_k0[0], c->ev_k1[0], open, blks))) return rc;
+    EDGE_T(9);
     return open ? wipe_failed(c->stream, n, blks, crc_mode, true) : 0;
 }
 
@@ -3759,6 +3813,23 @@ void jfsx_gen_key(uint64_t seed, uint64_t b, uint8_t key[32], uint8_t nonce[12])
     memcpy(nonce, &w0, 8);
     memcpy(nonce + 8, &w1, 4);
 }
+
+#ifdef JFSX_KS_PHASES
+// The last plain device-resident batch's step outside the main kernel, in
+// microseconds.  out[0..8]: the host's intervals between EdgeHost::t's ten
+// stamps; out[9..14]: on the stream, the upload, keysetup, keysetup's end to
+// the main kernel's start, the main kernel, finalize, the copy-back.
+int jfsx_debug_edge_host(double *out) {
+    if (!g_edge.ok) return -1;
+    for (int i = 0; i < 9; i++) out[i] = (g_edge.t[i + 1] - g_edge.t[i]) * 1e6;
+    for (int i = 0; i < 6; i++) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, g_edge.ev[i], g_edge.ev[i + 1]) != hipSuccess) return -1;
+        out[9 + i] = ms * 1e3;
+    }
+    return 0;
+}
+#endif
 
 // Host-only view of plan_batch (no device, no context), for tests: kind 0 GCM,
 // 1 ChaCha20-Poly1305, 2 CRC-only; tasks (nullable): up to cap triples

@@ -66,7 +66,15 @@ constexpr uint32_t kLdsSegFlag = kLdsSegRaw + 512;
 // P[256], P[257] repeat P[0], P[1] for the four-row period, whose last row runs
 // two lanes past the low byte's wrap
 constexpr uint32_t kLdsP = kLdsSegFlag + 512;
-constexpr uint32_t kLdsBytes = kLdsP + 4096 + 32;
+// the row split's cuts by wave age (gcm_task): 1024ths of a task in front of
+// wave w's run, w = 0..16, runs of 111 : 79 : 44 : 22 for waves 0-3, 4-7, 8-11
+// and 12-15; staged once per workgroup
+constexpr uint32_t kLdsCut = kLdsP + 4096 + 32;
+constexpr uint32_t kLdsBytes = kLdsCut + 80;
+__device__ __forceinline__ uint32_t cut_by_age(uint32_t w) {
+    const uint32_t g = w >> 2, i = w & 3;
+    return g == 0 ? 111 * i : g == 1 ? 444 + 79 * i : g == 2 ? 760 + 44 * i : g == 3 ? 936 + 22 * i : 1024u;
+}
 
 __device__ __forceinline__ uint32_t rotl8(uint32_t x) { return __builtin_amdgcn_alignbit(x, x, 24); }
 __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
@@ -506,16 +514,46 @@ struct GcmShape {
 // JFSX_KS_PHASES probe build: the workgroup running block 0's first task
 // stamps the 100 MHz clock at the main kernel's phase boundaries (g_main_ts:
 // kernel start, tables staged, GHASH table built, rows done, epilogue done,
-// task done); jfsx_debug_main_phases reads them back
+// task done); jfsx_debug_main_phases reads them back.  The stamps are thread
+// 0's and add no barrier: "rows done" and "epilogue done" are wave 0's.
+//
+// Behind them, the task edges (tools/taskedge_probe.py): workgroup 0 keeps one
+// record of kEdgeRec words for each of its first kEdgeTasks tasks.  Words 0-4
+// are thread 0's: the queue loop's top (behind its barrier), the first row
+// (behind the table build's barrier), the task's end (behind the shared-
+// segment sweep), the task's bytes and its index.  Words 8 + w and 24 + w are
+// wave w's own "rows done" and "epilogue done" (lane 0, no barrier), so the
+// skew between the waves shows.
 #ifdef JFSX_KS_PHASES
-__device__ unsigned long long g_main_ts[8];
+constexpr uint32_t kEdgeTasks = 8, kEdgeRec = 40;
+__device__ unsigned long long g_main_ts[8 + kEdgeTasks * kEdgeRec];
+// waves per SIMD that get rows (jfsx_debug_edge_waves; 4: the build's own split)
+__device__ uint32_t g_edge_waves = 4;
 #define MAIN_STAMP(cond, i)                                                                  \
     do {                                                                                     \
-        __syncthreads();                                                                     \
         if ((cond) && threadIdx.x == 0) g_main_ts[i] = __builtin_amdgcn_s_memrealtime(); \
+    } while (0)
+#define EDGE_PARAM , uint32_t edge_k
+#define EDGE_ARG(k) , (k)
+#define EDGE_PUT(word, val)                                                              \
+    do {                                                                                 \
+        if (edge_k < kEdgeTasks) g_main_ts[8 + edge_k * kEdgeRec + (word)] = (val); \
+    } while (0)
+#define EDGE_STAMP0(word)                                                    \
+    do {                                                                     \
+        if (threadIdx.x == 0) EDGE_PUT(word, __builtin_amdgcn_s_memrealtime()); \
+    } while (0)
+#define EDGE_STAMPW(word)                                                                     \
+    do {                                                                                      \
+        if ((threadIdx.x & 63) == 0) EDGE_PUT((word) + (threadIdx.x >> 6), __builtin_amdgcn_s_memrealtime()); \
     } while (0)
 #else
 #define MAIN_STAMP(cond, i) ((void)0)
+#define EDGE_PARAM
+#define EDGE_ARG(k)
+#define EDGE_PUT(word, val) ((void)0)
+#define EDGE_STAMP0(word) ((void)0)
+#define EDGE_STAMPW(word) ((void)0)
 #endif
 
 #ifdef JFSX_ABLATE_TRACE
@@ -535,7 +573,8 @@ template <bool OPEN, int CRCMODE, bool BS, int KL1>
 __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDev *__restrict__ blks,
                                          const GcmSched *__restrict__ sched, uint32_t *__restrict__ partial,
                                          uint32_t *__restrict__ pexp, const DevTables &tab, uint32_t tid,
-                                         uint32_t wave, uint32_t lane, uint32_t loff, const GhLane &gl, uint32_t xl) {
+                                         uint32_t wave, uint32_t lane, uint32_t loff, const GhLane &gl,
+                                         uint32_t xl EDGE_PARAM) {
 #ifdef JFSX_ABLATE_TRACE
     const uint64_t trace_t0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -590,12 +629,18 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
 
     const bool first_task = task.blk == 0 && task.c0 == 0;
     MAIN_STAMP(first_task, 2);
+    EDGE_STAMP0(1);
+    if (tid == 0) {
+        EDGE_PUT(3, task.c1 - task.c0);
+        EDGE_PUT(4, ((unsigned long long)task.blk << 32) | (task.c0 >> 16));
+    }
     const uint64_t c0 = task.c0, c1 = task.c1;
     const uint32_t nseg = (uint32_t)((c1 - c0 + kSeg - 1) / kSeg);
     constexpr uint32_t V = GcmShape<BS>::waves;  // waves (streams) per task
 
     // Row split (T-table kernel): the task's rows are cut into 16 contiguous
-    // runs of equal length, so a task of any size keeps every wave busy (a
+    // runs (equal in a task below 256 KiB, sized by wave age in a larger one,
+    // below), so a task of any size keeps every wave busy (a
     // 64 KiB block has 2 segments: with whole segments per wave 14 of 16
     // waves would idle).  A segment shared by two waves gets its CRC from
     // both waves' raw shares (crc_segment_end, task end below).  The
@@ -606,7 +651,33 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
         // in pairs of rows: every stream starts on an even row, as the two-row
         // loop's segment-end test assumes (only its second row can end a segment)
         const uint32_t npairs = (uint32_t)((c1 - c0 + 2047) / 2048);
-        const uint32_t ra = 2 * (wave * npairs / V), rb = 2 * ((wave + 1) * npairs / V);
+        // Wave w runs on SIMD w mod 4, and a SIMD serves its four waves oldest
+        // first: with equal runs waves 0-3 are done after half of the task's
+        // time and waves 12-15 run alone at its end, at 0.55 of the CU's
+        // four-wave row rate.  A task of 256 KiB or
+        // more is cut in proportion to the rates the four ages get while all
+        // are resident, 111 : 79 : 44 : 22 of 256, so that they end together.
+        // The rates are measured ones (Seal with the CRC, one MI355X), and
+        // both facts above are observed, not documented: tools/
+        // taskedge_probe.py shows every wave's end and re-derives the rates.
+        // The cuts come from a table staged once per workgroup (kLdsCut):
+        // worked out here, their arithmetic moved the register allocation of
+        // the row loops.  Equal runs are cuts at 64 w of 1024: 64 w npairs
+        // >> 10 is floor(w npairs / 16).
+        const bool byage = npairs >= 128;
+        const uint32_t *lc = reinterpret_cast<const uint32_t *>(lds + kLdsCut);
+        uint32_t ca = byage ? __builtin_amdgcn_readfirstlane(lc[wave]) : 64 * wave;
+        uint32_t cb = byage ? __builtin_amdgcn_readfirstlane(lc[wave + 1]) : 64 * (wave + 1);
+#ifdef JFSX_KS_PHASES
+        // probe: equal runs on the first 4k waves only, k = g_edge_waves < 4
+        // (the CU's row rate at k waves per SIMD, from which the weights come)
+        if (g_edge_waves < 4) {
+            const uint32_t vr = 4 * g_edge_waves;
+            ca = 1024 * (wave < vr ? wave : vr) / vr;
+            cb = 1024 * (wave + 1 < vr ? wave + 1 : vr) / vr;
+        }
+#endif
+        const uint32_t ra = 2 * (ca * npairs >> 10), rb = 2 * (cb * npairs >> 10);
         st.sub0 = c0 + (uint64_t)ra * 1024;
         st.sub1 = rb > ra ? (c0 + (uint64_t)rb * 1024 < c1 ? c0 + (uint64_t)rb * 1024 : c1) : st.sub0;
     } else {
@@ -1018,6 +1089,7 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
     }
 
     MAIN_STAMP(first_task, 3);
+    EDGE_STAMPW(8);
     // ---- stream epilogue: lift lane accumulators to the stream end, reduce ----
     const uint64_t nblk = (blk.len + 15) >> 4;
 #pragma unroll
@@ -1066,6 +1138,7 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
     }
 #endif
     MAIN_STAMP(first_task, 4);
+    EDGE_STAMPW(24);
     // ---- segments shared by two or more waves: sum the raw shares, finish ----
     if (CRCMODE && kRowSplit) {
         __syncthreads();
@@ -1088,6 +1161,7 @@ __device__ __forceinline__ void gcm_task(char *lds, const Task task, const BlkDe
         }
     }
     MAIN_STAMP(first_task, 5);
+    EDGE_STAMP0(2);
 }
 
 // gcm_main: persistent workgroups, one per CU (the LDS tables allow one),
@@ -1124,6 +1198,7 @@ __global__ __launch_bounds__(GcmShape<BS>::threads) void gcm_main_k(const Task *
             const uint4 *gt = reinterpret_cast<const uint4 *>(crc_composed(tab));
             if (tid < 256) reinterpret_cast<uint4 *>(lds + kLdsTT)[tid] = gt[tid];
         }
+        if (!BS && tid <= 16) reinterpret_cast<uint32_t *>(lds + kLdsCut)[tid] = cut_by_age(tid);
     }
 #ifdef JFSX_KS_PHASES
     __syncthreads();
@@ -1138,15 +1213,23 @@ __global__ __launch_bounds__(GcmShape<BS>::threads) void gcm_main_k(const Task *
     const GhLane gl = gh_lane(lane);
     const uint32_t xl = CRCMODE && !KL1 ? tab.crcx[lane] : 0u;  // (KL1: gcm_task loads it where it is used)
     if (tid == 0) s_task = atomicAdd(queue, 1u);
+#ifdef JFSX_KS_PHASES
+    uint32_t nth = 0;  // tasks this workgroup has taken
+#endif
     for (;;) {
         // also orders this task's table writes after the previous task's readers
         __syncthreads();
         const uint32_t ti = __builtin_amdgcn_readfirstlane(s_task);
         if (ti >= ntasks) break;  // the same for every wave: the queue is exhausted
+#ifdef JFSX_KS_PHASES
+        const uint32_t edge_k = blockIdx.x == 0 ? nth : kEdgeTasks;
+        nth++;
+        EDGE_STAMP0(0);
+#endif
         __syncthreads();          // every wave holds ti: s_task may take the next index
         if (tid == 0) s_task = atomicAdd(queue, 1u);  // the next task's index arrives during this one
         gcm_task<OPEN, CRCMODE, BS, KL1>(lds, tasks[ti], blks, sched, partial, pexp, tab, tid, wave, lane, loff, gl,
-                                         xl);
+                                         xl EDGE_ARG(edge_k));
     }
 }
 
@@ -1405,6 +1488,10 @@ __global__ __launch_bounds__(64) void gcm_keysetup_k(const KeyIn *__restrict__ k
 #ifdef JFSX_KS_PHASES
 extern "C" int jfsx_debug_main_phases(unsigned long long *out) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_main_ts), sizeof(g_main_ts)) == hipSuccess ? 0 : -1;
+}
+extern "C" int jfsx_debug_edge_waves(unsigned k) {
+    if (k < 1 || k > 4) return -1;
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_edge_waves), &k, sizeof(k)) == hipSuccess ? 0 : -1;
 }
 extern "C" int jfsx_debug_ks_phases(unsigned long long *out) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ks_ts), sizeof(g_ks_ts)) == hipSuccess ? 0 : -1;

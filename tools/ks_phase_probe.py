@@ -13,8 +13,10 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from juicefs_amd import engine as E  # noqa: E402
 
-MAIN = ["stage AES + CRC tables", "first task: GHASH table", "rows", "epilogue (lift, reduce)",
-        "shared-segment CRCs"]
+# (thread 0 stamps without a barrier in front: "rows" and "epilogue" are wave 0's own, and with runs sized by
+# wave age or equal runs wave 0 is not the last to finish; tools/taskedge_probe.py has every wave's)
+MAIN = ["stage AES + CRC tables", "first task: GHASH table", "rows (wave 0)", "epilogue (wave 0: lift, reduce)",
+        "wait for the other waves + shared-segment CRCs"]
 PHASES = ["stage AES tables", "key expansion", "bs masks, round-1 constants, k1", "E_K(0), E_K(J0)",
           "32 squarings H^(2^k)", "H^e (lane powers)", "basis x^i H^64", "init (len block)"]
 
@@ -36,7 +38,7 @@ def main():
     mf = getattr(eng.L, "jfsx_debug_main_phases", None)
     if mf is not None:
         mf.argtypes = [ctypes.c_void_p]
-    mts = (ctypes.c_ulonglong * 8)()
+    mts = (ctypes.c_ulonglong * (8 + 8 * 40))()  # the phases, then tools/taskedge_probe.py's task records
     macc = [0.0] * len(MAIN)
     for r in range(reps + 5):
         eng.seal_batch(E.AES256GCM, blks, nb, E.CRC_GEN, E.MEM_DEVICE)
