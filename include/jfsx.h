@@ -37,6 +37,9 @@
  *   JFSX_AES256GCM /     NewDataEncryptor algo "aes256gcm-rsa" /    pkg/object/encrypt.go:142-162
  *   JFSX_CHACHA20P1305   "chacha20-rsa"
  *
+ * RSA keys of 2048 and of 4096 bits are taken (jfsx_rsa_key_new), by every
+ * call that takes a jfsx_rsa_key; 3072 bits and every other size are refused
+ * there with JFSX_EINVAL and stay with the caller's own RSA.
  * RSA-OAEP key wrapping (encrypt.go:124-134) is a batch call of its own on
  * either side (jfsx_rsa_oaep_encrypt_batch / _decrypt_batch); the AEAD entry
  * points take the already-wrapped key bytes.  Randomness stays with the
@@ -451,14 +454,22 @@ uint32_t jfsx_crc32c_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
  * label) (pkg/object/encrypt.go:124-134, called at :207-210) for every object
  * of a batch at once, on the GPU.  The key is given by its CRT components
  * (Go's Primes[0], Primes[1], Precomputed.Dp, Dq, Qinv), big-endian,
- * prime_bytes each; RSA-2048 (prime_bytes = 128) only.  ct: host memory, item
- * i at ct + i*ct_stride, ct_len[i] bytes.  msg_len[i] = message length, or -1
- * for the decryption error (Go's "crypto/rsa: decryption error"); up to
- * msg_stride bytes of each message are copied to msg + i*msg_stride. */
+ * prime_bytes each.  Two key sizes are taken: RSA-2048 (prime_bytes = 128,
+ * modulus length k = 256) and RSA-4096 (prime_bytes = 256, k = 512), with odd
+ * primes whose top bit is set and dp, dq >= 2.  Every other prime_bytes (64,
+ * 192 for a 3072-bit key, 512, ...) is JFSX_EINVAL: such a volume keeps the
+ * host's rsa.DecryptOAEP / EncryptOAEP.  Keys of both sizes may be live on one
+ * context.  jfsx_rsa_key_bytes returns k (JFSX_EINVAL for a NULL key).
+ * ct: host memory, item i at ct + i*ct_stride, ct_len[i] <= k bytes (a shorter
+ * one is the big-endian integer it is; 0 or more than k bytes is the
+ * decryption error).  msg_len[i] = message length (up to k - 66), or -1 for
+ * the decryption error (Go's "crypto/rsa: decryption error"); up to msg_stride
+ * bytes of each message are copied to msg + i*msg_stride. */
 typedef struct jfsx_rsa_key jfsx_rsa_key;
 int jfsx_rsa_key_new(jfsx_ctx *ctx, const uint8_t *p, const uint8_t *q, const uint8_t *dp, const uint8_t *dq,
                      const uint8_t *qinv, int prime_bytes, const uint8_t *label, int label_len, jfsx_rsa_key **out);
 int jfsx_rsa_key_free(jfsx_rsa_key *key);
+int jfsx_rsa_key_bytes(const jfsx_rsa_key *key);
 int jfsx_rsa_oaep_decrypt_batch(jfsx_ctx *ctx, const jfsx_rsa_key *key, int n, const uint8_t *ct, uint64_t ct_stride,
                                 const uint32_t *ct_len, uint8_t *msg, uint64_t msg_stride, int32_t *msg_len);
 /* Batched RSA-OAEP key wrap, the write side of the unwrap: replaces, per
@@ -469,11 +480,12 @@ int jfsx_rsa_oaep_decrypt_batch(jfsx_ctx *ctx, const jfsx_rsa_key *key, int n, c
  * All pointers are host memory.  Item i reads msg_len[i] bytes at msg +
  * i*msg_stride and its 32-byte OAEP seed at seed + 32*i: the seeds are the
  * caller's randomness (Go reads them from rand), the engine draws none.  It
- * writes exactly 256 bytes at ct + i*ct_stride.  status[i] = 0, or -1 for Go's
- * "message too long for RSA key size" (msg_len[i] > 190; the 256 bytes are then
- * zero, the other items unaffected).  JFSX_EINVAL, before anything runs: null
- * seed, ct or status, ct_stride < 256, msg_len[i] > msg_stride, e out of range,
- * n < 0.  n == 0 returns 0. */
+ * writes exactly k = jfsx_rsa_key_bytes(key) bytes (256 or 512) at ct +
+ * i*ct_stride.  status[i] = 0, or -1 for Go's "message too long for RSA key
+ * size" (msg_len[i] > k - 66, that is 190 or 446; the k bytes are then zero,
+ * the other items unaffected).  JFSX_EINVAL, before anything runs: null seed,
+ * ct or status, ct_stride < k, msg_len[i] > msg_stride, e out of range, n < 0.
+ * n == 0 returns 0. */
 int jfsx_rsa_oaep_encrypt_batch(jfsx_ctx *ctx, const jfsx_rsa_key *key, uint32_t e, int n, const uint8_t *msg,
                                 uint64_t msg_stride, const uint32_t *msg_len, const uint8_t *seed /* n x 32 bytes */,
                                 uint8_t *ct, uint64_t ct_stride, int32_t *status);
@@ -701,10 +713,13 @@ int jfsx_store_batch(jfsx_ctx *ctx, int algo, int codec, int n, jfsx_sblk *blks,
  *   1 JFSX_CRC_CT: obj_crc != expect_crc               JFSX_ECRC
  *   2 cipher: hdr_len < 3 or != 3 + klen + nlen        JFSX_EHEADER
  *   3 cipher: the unwrap fails (also klen == 0,        JFSX_EKEY, key_len -1
- *     klen > 256, c >= n), or gives a message that     JFSX_EKEY, key_len = its length
+ *     klen > k, c >= n), or gives a message that       JFSX_EKEY, key_len = its length
  *     is not 32 bytes long
  *   4 cipher: nlen != 12, or the tag does not verify   JFSX_ETAG
  *   5 the decoder and length rows of jfsx_load_batch   JFSX_EFORMAT / JFSX_EDSTSIZE / JFSX_ESHORT
+ * (k = jfsx_rsa_key_bytes(key), Go's len(ciphertext) > k check: an object
+ * wrapped under a 2048-bit key and loaded with a 4096-bit one has klen = 256
+ * <= k, is unwrapped as the number it is, and fails the OAEP check: rule 3.)
  * out_len is as in jfsx_load_batch (0 for rules 1-4).  On any status other than
  * JFSX_OK the page and the CRC array are all zero.  obj_crc is the computed
  * value whenever JFSX_CRC_CT is set.  key_len is what the unwrap returned for
@@ -743,7 +758,8 @@ int jfsx_load_objects(jfsx_ctx *ctx, const jfsx_rsa_key *key, int algo, int code
 /* One-call object store: the write side of jfsx_load_objects -- from the page
  * to the stored object that store.put hands to the object store
  * (dataEncryptor.Encrypt, pkg/object/encrypt.go:164-194):
- *   BE16(256) | 12 | wrapped key (256) | nonce (12) | C | tag (16)
+ *   BE16(k) | 12 | wrapped key (k) | nonce (12) | C | tag (16)
+ * (k = jfsx_rsa_key_bytes(key): 256, or 512 with a 4096-bit key)
  * for a batch of pages in one synchronous call: the page's verify or
  * checksum(), rsaEncryptor.Encrypt of the data key (encrypt.go:169), Compress,
  * Seal, the header and tag around C, and the object store's checksum of all of
@@ -760,14 +776,16 @@ int jfsx_load_objects(jfsx_ctx *ctx, const jfsx_rsa_key *key, int algo, int code
  *             JFSX_CRC_CT OR'ed in or given alone for obj_crc
  *   mem       JFSX_MEM_HOST: pageable or pinned memory at any alignment; only
  *             obj[0, out_len) is written.  JFSX_MEM_DEVICE: (uintptr_t)obj % 16
- *             == 1, so that C at obj + 271 is 16-byte aligned and the wrapped
- *             key at obj + 3 and the nonce at obj + 259 are dword aligned; src
+ *             == 1, so that C at obj + 15 + k is 16-byte aligned (15 + k is
+ *             15 mod 16 for k = 256 and for k = 512: one rule for both key
+ *             sizes) and the wrapped key at obj + 3 and the nonce at obj + 3
+ *             + k are dword aligned; src
  *             16-byte aligned when a page CRC or the Seal reads it (GEN /
  *             VERIFY, or JFSX_CODEC_NONE); obj distinct from src; crc in device
  *             memory
  * JFSX_EINVAL before anything runs, with the records untouched: anything else,
  * the limits of the separate calls, reserved != 0, obj_cap below
- * jfsx_object_bound(codec, len), a NULL crc with GEN / VERIFY, a NULL key, a
+ * jfsx_object_bound_key(key, codec, len), a NULL crc with GEN / VERIFY, a NULL key, a
  * key of another device, e out of range.  The bytes are those of the separate
  * calls: jfsx_rsa_oaep_encrypt_batch on key and seed, the compressor, then
  * jfsx_seal_batch with key and nonce.  A page that fails JFSX_CRC_VERIFY gets
@@ -778,10 +796,16 @@ int jfsx_load_objects(jfsx_ctx *ctx, const jfsx_rsa_key *key, int algo, int code
  * are verified, else twice, as jfsx_store_batch.  jfsx_metrics counts crc_*
  * over the n pages (GEN / VERIFY), lz4c_* / zstdc_* and seal_* over the blocks
  * that passed the verify (seal_bytes = the sum of img_len). */
+/* the header of an RSA-2048 volume's object; with another key it is 15 +
+ * jfsx_rsa_key_bytes(key) (527 at 4096 bits) */
 #define JFSX_OBJ_HDR_BYTES 271 /* BE16(256) | 12 | 256-byte wrapped key | 12-byte nonce */
 #define JFSX_OBJ_TAG_BYTES 16
-/* 271 + (len | jfsx_lz4_bound(len) | jfsx_zstd_bound(len)) + 16; 0 for an unknown codec */
+/* 271 + (len | jfsx_lz4_bound(len) | jfsx_zstd_bound(len)) + 16; 0 for an unknown
+ * codec.  An RSA-2048 volume's bound: it is too small for a 4096-bit key, and
+ * jfsx_store_objects answers it with JFSX_EINVAL there. */
 uint64_t jfsx_object_bound(int codec, uint64_t len);
+/* the same for key: (15 + k) + image bound + 16; 0 for a NULL key or an unknown codec */
+uint64_t jfsx_object_bound_key(const jfsx_rsa_key *key, int codec, uint64_t len);
 typedef struct jfsx_soblk {
     uint8_t key[32];      /* data key: the caller's randomness (encrypt.go:165) */
     uint8_t nonce[12];    /* encrypt.go:177                                     */
@@ -790,7 +814,7 @@ typedef struct jfsx_soblk {
     const void *src;      /* the page                                           */
     uint64_t len;
     void *obj;            /* out: header | C | tag, contiguous                  */
-    uint64_t obj_cap;     /* >= jfsx_object_bound(codec, len)                   */
+    uint64_t obj_cap;     /* >= jfsx_object_bound_key(key, codec, len)          */
     uint8_t *crc;         /* page CRCs. GEN: out, VERIFY: in; unused otherwise  */
     uint64_t out_len;     /* out: bytes of the object, 0 for a failed block     */
     uint64_t img_len;     /* out: bytes of C                                    */

@@ -18,6 +18,7 @@
 #include <chrono>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <shared_mutex>
@@ -3882,27 +3883,38 @@ int jfsx_debug_crc_composed(uint32_t *tt, uint32_t *xlb) {
 // ---------------------------------------------------------------------------
 struct jfsx_rsa_key {
     int device = 0;
-    jfsx_rsa::Key *d_key = nullptr;
+    int kbytes = 0;         // modulus length k: 256 (d_key is a jfsx_rsa::Key) or 512 (a jfsx_rsa::KeyW)
+    void *d_key = nullptr;
 };
 
 int jfsx_rsa_key_new(jfsx_ctx *c, const uint8_t *p, const uint8_t *q, const uint8_t *dp, const uint8_t *dq,
                      const uint8_t *qinv, int prime_bytes, const uint8_t *label, int label_len, jfsx_rsa_key **out) {
     if (!c || !out || !p || !q || !dp || !dq || !qinv || label_len < 0 || (label_len && !label)) return JFSX_EINVAL;
     *out = nullptr;
-    if (prime_bytes != 4 * jfsx_rsa::kLimbs) return JFSX_EINVAL;  // RSA-2048 (1024-bit primes)
-    jfsx_rsa::Key k;
+    // RSA-2048 (1024-bit primes) or RSA-4096 (2048-bit primes); no other size
+    const bool wide = prime_bytes == 4 * jfsx_rsa::kLimbsW;
+    if (!wide && prime_bytes != 4 * jfsx_rsa::kLimbs) return JFSX_EINVAL;
+    // one record of either width, on the heap (KeyW is 5 KiB)
+    std::unique_ptr<jfsx_rsa::Key> k2(wide ? nullptr : new jfsx_rsa::Key());
+    std::unique_ptr<jfsx_rsa::KeyW> kw(wide ? new jfsx_rsa::KeyW() : nullptr);
     const uint8_t empty = 0;
-    if (!jfsx_rsa::key_setup(k, p, q, dp, dq, qinv, label_len ? label : &empty, label_len)) return JFSX_EINVAL;
+    const uint8_t *lab = label_len ? label : &empty;
+    if (wide ? !jfsx_rsa::key_setup_w(*kw, p, q, dp, dq, qinv, lab, label_len)
+             : !jfsx_rsa::key_setup(*k2, p, q, dp, dq, qinv, lab, label_len))
+        return JFSX_EINVAL;
+    const void *rec = wide ? (const void *)kw.get() : (const void *)k2.get();
+    const size_t rec_bytes = wide ? sizeof(jfsx_rsa::KeyW) : sizeof(jfsx_rsa::Key);
     std::lock_guard<std::mutex> g(c->mu);
     CtxScope es_(c);
     HIP_OK(hipSetDevice(c->device));
     jfsx_rsa_key *rk = new jfsx_rsa_key();
     rk->device = c->device;
-    if (hipMalloc((void **)&rk->d_key, sizeof(k)) != hipSuccess) {
+    rk->kbytes = wide ? jfsx_rsa::kModBytesW : jfsx_rsa::kModBytes;
+    if (hipMalloc((void **)&rk->d_key, rec_bytes) != hipSuccess) {
         delete rk;
         return JFSX_ENOMEM;
     }
-    if (hipMemcpy(rk->d_key, &k, sizeof(k), hipMemcpyHostToDevice) != hipSuccess) {
+    if (hipMemcpy(rk->d_key, rec, rec_bytes, hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipFree(rk->d_key);
         delete rk;
         return JFSX_EIO;
@@ -3919,13 +3931,15 @@ int jfsx_rsa_key_free(jfsx_rsa_key *k) {
     return 0;
 }
 
+int jfsx_rsa_key_bytes(const jfsx_rsa_key *k) { return k ? k->kbytes : JFSX_EINVAL; }
+
 int jfsx_rsa_oaep_decrypt_batch(jfsx_ctx *c, const jfsx_rsa_key *k, int n, const uint8_t *ct, uint64_t ct_stride,
                                 const uint32_t *ct_len, uint8_t *msg, uint64_t msg_stride, int32_t *msg_len) {
     if (!c || !k || n < 0 || (n && (!ct || !ct_len || !msg_len || (msg_stride && !msg)))) return JFSX_EINVAL;
     if (n == 0) return 0;
     if (k->device != c->device) return JFSX_EINVAL;
-    constexpr size_t K = jfsx_rsa::kModBytes;
-    const size_t o_ct = 0, o_mh = align256(K * n), o_em = o_mh + align256(2 * 4 * jfsx_rsa::kLimbs * (size_t)n),
+    const size_t K = (size_t)k->kbytes;
+    const size_t o_ct = 0, o_mh = align256(K * n), o_em = o_mh + align256(4 * rsa_mh_words(k->kbytes) * (size_t)n),
                  o_len = o_em + align256(K * n), dbytes = o_len + align256(4 * (size_t)n);
     const size_t hbytes = align256(K * n) + align256(4 * (size_t)n);
     std::lock_guard<std::mutex> g(c->mu);
@@ -3945,7 +3959,7 @@ int jfsx_rsa_oaep_decrypt_batch(jfsx_ctx *c, const jfsx_rsa_key *k, int n, const
     char *d = c->rsa_d;
     HIP_OK(hipMemcpyAsync(d + o_ct, c->rsa_h, K * n, hipMemcpyHostToDevice, c->stream));
     launch_begin();
-    launch_rsa_unwrap(c->stream, k->d_key, n, (const uint8_t *)(d + o_ct), (uint32_t *)(d + o_mh),
+    launch_rsa_unwrap(c->stream, k->d_key, k->kbytes, n, (const uint8_t *)(d + o_ct), (uint32_t *)(d + o_mh),
                       (uint8_t *)(d + o_em), (int32_t *)(d + o_len));
     HIP_OK(hipGetLastError());
     char *hl = c->rsa_h + align256(K * n);
@@ -3966,8 +3980,9 @@ int jfsx_rsa_oaep_decrypt_batch(jfsx_ctx *c, const jfsx_rsa_key *k, int n, const
 int jfsx_rsa_oaep_encrypt_batch(jfsx_ctx *c, const jfsx_rsa_key *k, uint32_t e, int n, const uint8_t *msg,
                                 uint64_t msg_stride, const uint32_t *msg_len, const uint8_t *seed, uint8_t *ct,
                                 uint64_t ct_stride, int32_t *status) {
-    constexpr size_t K = jfsx_rsa::kModBytes, S = kRsaWrapSlot, H = jfsx_rsa::kHash;
+    constexpr size_t H = jfsx_rsa::kHash;
     if (!c || !k || n < 0 || e < jfsx_rsa::kMinE || e > jfsx_rsa::kMaxE) return JFSX_EINVAL;  // e: Go's checkPub
+    const size_t K = (size_t)k->kbytes, S = (size_t)rsa_wrap_slot(k->kbytes);
     if (n == 0) return 0;
     if (!msg_len || !seed || !ct || !status || ct_stride < K) return JFSX_EINVAL;
     for (int i = 0; i < n; i++)
@@ -3975,8 +3990,8 @@ int jfsx_rsa_oaep_encrypt_batch(jfsx_ctx *c, const jfsx_rsa_key *k, uint32_t e, 
     if (k->device != c->device) return JFSX_EINVAL;
     // device: msg slots | seeds | lengths (one copy in) | EM limbs | ct (one copy out)
     const size_t o_msg = 0, o_seed = align256(S * n), o_len = o_seed + align256(H * n),
-                 inbytes = o_len + align256(4 * (size_t)n), o_em = inbytes, o_ct = o_em + align256(K * n),
-                 dbytes = o_ct + align256(K * n);
+                 inbytes = o_len + align256(4 * (size_t)n), o_em = inbytes,
+                 o_ct = o_em + align256(4 * rsa_em_words(k->kbytes) * (size_t)n), dbytes = o_ct + align256(K * n);
     const size_t hbytes = std::max(inbytes, K * n);
     std::lock_guard<std::mutex> g(c->mu);
     CtxScope es_(c);
@@ -3987,8 +4002,8 @@ int jfsx_rsa_oaep_encrypt_batch(jfsx_ctx *c, const jfsx_rsa_key *k, uint32_t e, 
     char *h = c->rsa_h;
     memset(h, 0, inbytes);
     for (int i = 0; i < n; i++) {
-        // Go: "message too long for RSA key size"; the kernels give such an item 256 zero bytes
-        status[i] = msg_len[i] > (uint32_t)jfsx_rsa::kMaxMsg ? -1 : 0;
+        // Go: "message too long for RSA key size"; the kernels give such an item k zero bytes
+        status[i] = msg_len[i] > (uint32_t)(K - 2 * H - 2) ? -1 : 0;
         if (status[i] == 0 && msg_len[i]) memcpy(h + o_msg + S * i, msg + msg_stride * i, msg_len[i]);
         memcpy(h + o_seed + H * i, seed + H * i, H);
         ((uint32_t *)(h + o_len))[i] = msg_len[i];
@@ -3996,7 +4011,7 @@ int jfsx_rsa_oaep_encrypt_batch(jfsx_ctx *c, const jfsx_rsa_key *k, uint32_t e, 
     char *d = c->rsa_d;
     HIP_OK(hipMemcpyAsync(d, h, inbytes, hipMemcpyHostToDevice, c->stream));
     launch_begin();
-    launch_rsa_wrap(c->stream, k->d_key, e, n, (const uint8_t *)(d + o_msg), (const uint32_t *)(d + o_len),
+    launch_rsa_wrap(c->stream, k->d_key, k->kbytes, e, n, (const uint8_t *)(d + o_msg), (const uint32_t *)(d + o_len),
                     (const uint8_t *)(d + o_seed), (uint32_t *)(d + o_em), (uint8_t *)(d + o_ct));
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpyAsync(h, d + o_ct, K * n, hipMemcpyDeviceToHost, c->stream));
@@ -4066,7 +4081,8 @@ int objects_enqueue(jfsx_ctx *c, const jfsx_rsa_key *key, int algo, int codec, i
     const bool ct = st.ct = (crc_mode & JFSX_CRC_CT) != 0;
     const bool coded = st.coded = codec != JFSX_CODEC_NONE;
     const bool zstd = codec == JFSX_CODEC_ZSTD;
-    constexpr size_t K = jfsx_rsa::kModBytes;
+    const int kbytes = key ? key->kbytes : jfsx_rsa::kModBytes;  // the modulus length k of the volume's key
+    const size_t K = (size_t)kbytes;
     std::vector<size_t> ioff(n);
     st.poff.assign(n, 0);
     st.out_b.assign(n, 0);
@@ -4099,7 +4115,7 @@ int objects_enqueue(jfsx_ctx *c, const jfsx_rsa_key *key, int algo, int codec, i
     st.st_off = o_st - o_res;
     st.crc_off = o_crc - o_res;
     // the unwrap's workspace, as jfsx_rsa_oaep_decrypt_batch lays it out
-    const size_t r_ct = 0, r_mh = align256(K * n), r_em = r_mh + align256(2 * 4 * jfsx_rsa::kLimbs * (size_t)n),
+    const size_t r_ct = 0, r_mh = align256(K * n), r_em = r_mh + align256(4 * rsa_mh_words(kbytes) * (size_t)n),
                  r_len = r_em + align256(K * n), r_bytes = r_len + align256(4 * (size_t)n);
     int rc;
     // every buffer of the path before the first enqueue
@@ -4239,8 +4255,8 @@ int objects_enqueue(jfsx_ctx *c, const jfsx_rsa_key *key, int algo, int codec, i
     // 3. the unwrap, 4. the fold
     launch_begin();
     if (aead)
-        launch_rsa_unwrap(s, key->d_key, n, (const uint8_t *)(r + r_ct), (uint32_t *)(r + r_mh), (uint8_t *)(r + r_em),
-                          (int32_t *)(r + r_len));
+        launch_rsa_unwrap(s, key->d_key, kbytes, n, (const uint8_t *)(r + r_ct), (uint32_t *)(r + r_mh),
+                          (uint8_t *)(r + r_em), (int32_t *)(r + r_len));
     if (ct) launch_obj_fold(s, n, dob, aead ? 16 : 0, c->tabs.crcx + 64, dst);
     HIP_OK(hipGetLastError());
     // 5. the keys into Open's KeyIn[n], 6. Open: into the staging buffer for
@@ -4248,7 +4264,7 @@ int objects_enqueue(jfsx_ctx *c, const jfsx_rsa_key *key, int algo, int codec, i
     const BlkOut *opened = nullptr;
     if (aead) {
         const KeyHook hook = [&](hipStream_t ks, KeyIn *dk) {
-            launch_obj_keys(ks, n, dob, dst, (uint8_t *)(r + r_em), (const int32_t *)(r + r_len), dk);
+            launch_obj_keys(ks, n, dob, dst, (uint8_t *)(r + r_em), kbytes, (const int32_t *)(r + r_len), dk);
         };
         if ((rc = enqueue_aead(c, c->load_aead, s, c->load_ev[0], c->load_ev[1], algo, true, n, ab.data(),
                                !coded && crc ? JFSX_CRC_GEN : JFSX_CRC_NONE, nullptr, nullptr, false, nullptr, nullptr,
@@ -4401,17 +4417,23 @@ extern "C" int jfsx_load_objects(jfsx_ctx *c, const jfsx_rsa_key *key, int algo,
 // ---------------------------------------------------------------------------
 namespace {
 
-constexpr uint64_t kObjFrame = JFSX_OBJ_HDR_BYTES + JFSX_OBJ_TAG_BYTES;
+// header and tag around C for a key whose modulus is kbytes long: 287, or 543
+// with a 4096-bit key.  15 + kbytes is 15 mod 16 for both, so the rule "obj is
+// 1 mod 16" puts C on 16 bytes at either width.
+constexpr uint64_t obj_hdr(int kbytes) { return 3 + (uint64_t)kbytes + 12; }
+constexpr uint64_t obj_frame(int kbytes) { return obj_hdr(kbytes) + JFSX_OBJ_TAG_BYTES; }
+static_assert(obj_hdr(jfsx_rsa::kModBytes) == JFSX_OBJ_HDR_BYTES, "the public header's RSA-2048 figure");
+static_assert(obj_hdr(jfsx_rsa::kModBytes) % 16 == 15 && obj_hdr(jfsx_rsa::kModBytesW) % 16 == 15, "C's alignment");
 // a host batch's object in the packed device image and in the bounce buffer:
 // one byte into a 16-byte aligned slot, so that C is 16-byte aligned
 constexpr size_t kObjLead = 1;
-inline size_t obj_slot(uint64_t img_len) { return align16(kObjLead + kObjFrame + img_len); }
+inline size_t obj_slot(int kbytes, uint64_t img_len) { return align16(kObjLead + obj_frame(kbytes) + img_len); }
 
-uint64_t object_bound(int codec, uint64_t len) {
+uint64_t object_bound(int kbytes, int codec, uint64_t len) {
     if (codec != JFSX_CODEC_NONE && codec != JFSX_CODEC_LZ4 && codec != JFSX_CODEC_ZSTD) return 0;
     const uint64_t img = codec == JFSX_CODEC_ZSTD ? zstd_bound(len) : codec == JFSX_CODEC_LZ4 ? lz4_bound(len) : len;
     if (codec == JFSX_CODEC_LZ4 && !img) return 0;  // past jfsx_lz4_bound's domain
-    return kObjFrame + img;
+    return obj_frame(kbytes) + img;
 }
 
 int check_sobj_args(const jfsx_rsa_key *key, uint32_t e, int algo, int codec, int n, const jfsx_soblk *blks,
@@ -4430,7 +4452,9 @@ int check_sobj_args(const jfsx_rsa_key *key, uint32_t e, int algo, int codec, in
         const uint64_t img = codec == JFSX_CODEC_ZSTD ? zstd_bound(b.len) : coded ? lz4_bound(b.len) : b.len;
         if (algo == JFSX_AES256GCM && img > kGcmMaxLen) return JFSX_EINVAL;
         if (algo == JFSX_CHACHA20P1305 && img > kCpMaxLen) return JFSX_EINVAL;
-        if (b.obj_cap < kObjFrame + img) return JFSX_EINVAL;
+        // the smallest bound of any key: the key itself is not looked at here
+        // (check_sobj_caps has its bound, once the key is known to be one)
+        if (b.obj_cap < obj_frame(jfsx_rsa::kModBytes) + img) return JFSX_EINVAL;
         if (page_crc && !b.crc) return JFSX_EINVAL;
         if (mem == JFSX_MEM_DEVICE) {
             if (((uintptr_t)b.obj & 15) != 1) return JFSX_EINVAL;
@@ -4442,6 +4466,14 @@ int check_sobj_args(const jfsx_rsa_key *key, uint32_t e, int algo, int codec, in
     return 0;
 }
 
+// obj_cap against the key's own bound (543 + the image bound at 4096 bits);
+// the blocks have passed check_sobj_args
+int check_sobj_caps(const jfsx_rsa_key *key, int codec, int n, const jfsx_soblk *blks) {
+    for (int i = 0; i < n; i++)
+        if (blks[i].obj_cap < object_bound(key->kbytes, codec, blks[i].len)) return JFSX_EINVAL;
+    return 0;
+}
+
 struct SobjState {
     StoreState st;
     std::vector<StoreRes> res;     // per block: what phase A found (wait #1), or OK / len without one
@@ -4450,18 +4482,21 @@ struct SobjState {
     int seal_mult = 1;
     size_t out_bytes = 0;
     size_t o_msg = 0, o_ct = 0, msg_bytes = 0;  // the wrap's workspace
+    int kbytes = 0;                             // the key's modulus length: the wrapped key in every header
     size_t h_sres = 0;                          // the downloaded SobjRes[m] in store_h
 };
 // jfsx_compact_objects: more downloads behind phase B's, in front of its wait
 using SobjTail = std::function<int(const SobjState &)>;
 
 // The wrap, in jfsx_rsa_oaep_encrypt_batch's layout: msg | seed | len up in
-// one copy, the 256-byte results left at o_ct.
+// one copy, the k-byte results left at o_ct.
 int sobj_wrap(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t e, int n, const jfsx_soblk *blks, SobjState &so) {
-    constexpr size_t K = jfsx_rsa::kModBytes, S = kRsaWrapSlot, H = jfsx_rsa::kHash;
+    constexpr size_t H = jfsx_rsa::kHash;
+    const size_t K = (size_t)key->kbytes, S = (size_t)rsa_wrap_slot(key->kbytes);
     const size_t o_msg = 0, o_seed = align256(S * n), o_len = o_seed + align256(H * n),
-                 inbytes = o_len + align256(4 * (size_t)n), o_em = inbytes, o_ct = o_em + align256(K * n),
-                 dbytes = o_ct + align256(K * n);
+                 inbytes = o_len + align256(4 * (size_t)n), o_em = inbytes,
+                 o_ct = o_em + align256(4 * rsa_em_words(key->kbytes) * (size_t)n), dbytes = o_ct + align256(K * n);
+    so.kbytes = key->kbytes;
     int rc;
     if ((rc = ensure_dev(c, &c->rsa_d, &c->rsa_dcap, dbytes))) return rc;
     if ((rc = ensure_host(&c->rsa_h, &c->rsa_hcap, std::max(inbytes, K * n)))) return rc;
@@ -4477,8 +4512,9 @@ int sobj_wrap(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t e, int n, const jfs
     so.msg_bytes = S * n;
     HIP_OK(hipMemcpyAsync(d, h, inbytes, hipMemcpyHostToDevice, c->stream));
     launch_begin();
-    launch_rsa_wrap(c->stream, key->d_key, e, n, (const uint8_t *)(d + o_msg), (const uint32_t *)(d + o_len),
-                    (const uint8_t *)(d + o_seed), (uint32_t *)(d + o_em), (uint8_t *)(d + o_ct));
+    launch_rsa_wrap(c->stream, key->d_key, key->kbytes, e, n, (const uint8_t *)(d + o_msg),
+                    (const uint32_t *)(d + o_len), (const uint8_t *)(d + o_seed), (uint32_t *)(d + o_em),
+                    (uint8_t *)(d + o_ct));
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -4496,7 +4532,7 @@ int sobj_phase_b(jfsx_ctx *c, int algo, int n, const jfsx_soblk *blks, SobjState
         if (so.res[i].status != JFSX_OK) continue;
         st.okidx.push_back(i);
         st.ooff[i] = out_bytes;
-        out_bytes += obj_slot(so.res[i].out_len);
+        out_bytes += obj_slot(so.kbytes, so.res[i].out_len);
     }
     so.out_bytes = out_bytes;
     const int m = (int)st.okidx.size();
@@ -4529,7 +4565,7 @@ int sobj_phase_b(jfsx_ctx *c, int algo, int n, const jfsx_soblk *blks, SobjState
         memset(&a, 0, sizeof(a));
         a.src = st.plain ? (!b.len ? nullptr : host ? (const void *)(c->store_stage + st.poff[i]) : b.src)
                          : (const void *)(st.slots + st.zoff[i]);
-        a.dst = obj + JFSX_OBJ_HDR_BYTES;
+        a.dst = obj + obj_hdr(so.kbytes);
         a.len = img_len;
         memcpy(a.nonce, b.nonce, 12);  // the key comes from the wrap's message slot (sobj_keys_k)
         a.crc = seal_mode ? crc_unused : nullptr;
@@ -4546,7 +4582,7 @@ int sobj_phase_b(jfsx_ctx *c, int algo, int n, const jfsx_soblk *blks, SobjState
     const SobjBlk *dsb = (const SobjBlk *)(d + o_sb);
     HIP_OK(hipMemcpyAsync(d + o_sb, c->store_h + o_sb, sizeof(SobjBlk) * m, hipMemcpyHostToDevice, s));
     const uint8_t *msg = (const uint8_t *)(c->rsa_d + so.o_msg);
-    const KeyHook hook = [&](hipStream_t ks, KeyIn *dk) { launch_sobj_keys(ks, m, dsb, msg, dk); };
+    const KeyHook hook = [&](hipStream_t ks, KeyIn *dk) { launch_sobj_keys(ks, m, dsb, msg, so.kbytes, dk); };
     if ((rc = enqueue_aead(c, c->store_aead, s, c->store_ev[2], c->store_ev[3], algo, false, m, st.sb.data(),
                            seal_mode, nullptr, nullptr, false, nullptr, nullptr, seal_mode != 0, false, nullptr,
                            nullptr, &hook)))
@@ -4554,7 +4590,7 @@ int sobj_phase_b(jfsx_ctx *c, int algo, int n, const jfsx_soblk *blks, SobjState
     Workspace &w = c->store_aead;
     const uint8_t *words = (const uint8_t *)w.dout + w.crc_off;
     launch_begin();
-    launch_sobj_frame(s, m, dsb, (const uint8_t *)(c->rsa_d + so.o_ct), (const BlkOut *)w.dout, st.ct ? words : nullptr,
+    launch_sobj_frame(s, m, dsb, (const uint8_t *)(c->rsa_d + so.o_ct), so.kbytes, (const BlkOut *)w.dout, st.ct ? words : nullptr,
                       st.ct, c->tabs.crcx + 64, (SobjRes *)(d + o_res));
     HIP_OK(hipGetLastError());
     // the keys have reached the Seal's schedules: no copy stays in the wrap's workspace
@@ -4583,7 +4619,7 @@ int sobj_phase_b(jfsx_ctx *c, int algo, int n, const jfsx_soblk *blks, SobjState
             for (int i : st.okidx) {
                 const size_t at = st.ooff[i] + kObjLead;
                 HIP_OK(hipMemcpyAsync(st.out_b[i] ? st.bounce + at : (char *)blks[i].obj, c->store_img + at,
-                                      kObjFrame + so.res[i].out_len, hipMemcpyDeviceToHost, s));
+                                      obj_frame(so.kbytes) + so.res[i].out_len, hipMemcpyDeviceToHost, s));
             }
         }
     }
@@ -4602,7 +4638,7 @@ int run_store_objects(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t e, int algo
     st.zstd = codec == JFSX_CODEC_ZSTD;
     st.plain = codec == JFSX_CODEC_NONE;
     st.page_mode = crc_mode & 3;
-    st.obj_extra = kObjLead + kObjFrame + 15;
+    st.obj_extra = kObjLead + obj_frame(key->kbytes) + 15;
     auto wait = [&](const char *what) {
         const hipError_t se = hipStreamSynchronize(c->stream);
         if (!rc && se != hipSuccess) {
@@ -4618,7 +4654,7 @@ int run_store_objects(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t e, int algo
         b.src = blks[i].src;
         b.len = blks[i].len;
         b.dst = blks[i].obj;
-        b.dst_cap = blks[i].obj_cap - kObjFrame;
+        b.dst_cap = blks[i].obj_cap - obj_frame(key->kbytes);
         b.crc = blks[i].crc;
     }
     const bool verify = st.page_mode == JFSX_CRC_VERIFY, wait1 = !st.plain || verify;
@@ -4736,7 +4772,12 @@ int run_store_objects(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t e, int algo
 
 }  // namespace
 
-extern "C" uint64_t jfsx_object_bound(int codec, uint64_t len) { return object_bound(codec, len); }
+extern "C" uint64_t jfsx_object_bound(int codec, uint64_t len) {
+    return object_bound(jfsx_rsa::kModBytes, codec, len);  // an RSA-2048 volume's
+}
+extern "C" uint64_t jfsx_object_bound_key(const jfsx_rsa_key *key, int codec, uint64_t len) {
+    return key ? object_bound(key->kbytes, codec, len) : 0;
+}
 
 extern "C" int jfsx_store_objects(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t e, int algo, int codec, int n,
                                   jfsx_soblk *blks, int crc_mode, int mem) {
@@ -4744,7 +4785,7 @@ extern "C" int jfsx_store_objects(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t
     // argument errors before the context, the key or the device is touched
     const int rc = check_sobj_args(key, e, algo, codec, n, blks, crc_mode, mem);
     if (rc || n == 0) return rc;
-    if (key->device != c->device) return JFSX_EINVAL;
+    if (key->device != c->device || check_sobj_caps(key, codec, n, blks)) return JFSX_EINVAL;
     std::lock_guard<std::mutex> g(c->mu);
     CtxScope es_(c);
     HIP_OK(hipSetDevice(c->device));
@@ -5027,7 +5068,7 @@ int run_compact(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t e, int algo, int 
     for (int i = 0; i < n_src; i++) soff[i] = off, off += align256(src[i].len);
     for (int j = 0; j < n_dst; j++) doff[j] = off, off += align256(dst[j].len);
     const size_t o_obj = off;
-    for (int j = 0; j < n_dst; j++) ooff[j] = off - o_obj, off += align256(kObjLead + object_bound(codec, dst[j].len));
+    for (int j = 0; j < n_dst; j++) ooff[j] = off - o_obj, off += align256(kObjLead + object_bound(key->kbytes, codec, dst[j].len));
     const size_t obj_bytes = off - o_obj, o_crc = off;
     for (int j = 0; j < n_dst; j++) coff[j] = off - o_crc, off += gen ? 4 * nseg_of(dst[j].len) : 0;
     const size_t crc_bytes = off - o_crc;
@@ -5114,13 +5155,14 @@ int run_compact(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t e, int algo, int 
         so[k] = dst[j];
         so[k].src = dst[j].len ? d + doff[j] : nullptr;
         so[k].obj = d + o_obj + ooff[j] + kObjLead;
-        so[k].obj_cap = object_bound(codec, dst[j].len);
+        so[k].obj_cap = object_bound(key->kbytes, codec, dst[j].len);
         so[k].crc = gen ? (uint8_t *)(d + o_crc + coff[j]) : nullptr;
     }
     const SobjTail tail = [&](const SobjState &ss) {
         for (int k : ss.st.okidx) {
             const size_t at = ooff[good[k]] + kObjLead;
-            HIP_OK(hipMemcpyAsync(bounce + at, d + o_obj + at, kObjFrame + ss.res[k].out_len, hipMemcpyDeviceToHost, s));
+            HIP_OK(hipMemcpyAsync(bounce + at, d + o_obj + at, obj_frame(key->kbytes) + ss.res[k].out_len,
+                                  hipMemcpyDeviceToHost, s));
         }
         if (crc_bytes)
             HIP_OK(hipMemcpyAsync(bounce + align256(obj_bytes), d + o_crc, crc_bytes, hipMemcpyDeviceToHost, s));
@@ -5183,7 +5225,7 @@ extern "C" int jfsx_compact_objects(jfsx_ctx *c, const jfsx_rsa_key *key, uint32
     if ((rc = check_sobj_args(key, e, algo, codec, n_dst, so.data(), dst_crc_mode, JFSX_MEM_HOST))) return rc;
     if ((rc = check_pieces(n_src, slen.data(), n_dst, dlen.data(), runs.data(), n_piece, pieces))) return rc;
     if (n_dst == 0) return 0;
-    if (key->device != c->device) return JFSX_EINVAL;
+    if (key->device != c->device || check_sobj_caps(key, codec, n_dst, dst)) return JFSX_EINVAL;
     std::lock_guard<std::mutex> g(c->mu);
     CtxScope es_(c);
     HIP_OK(hipSetDevice(c->device));

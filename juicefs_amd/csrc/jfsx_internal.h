@@ -358,9 +358,9 @@ struct ObjState {  // copied back to the host
 void launch_obj_fold(hipStream_t s, int n, const ObjBlk *ob, uint32_t tail, const uint32_t *x8pow, ObjState *st);
 // one thread per object: the 32-byte unwrap result of a block that passed
 // rules 1-3 into keys[i].key (zeros otherwise), key_len into st, the unwrap's
-// message slot (em, 256 bytes per object) zeroed
-void launch_obj_keys(hipStream_t s, int n, const ObjBlk *ob, ObjState *st, uint8_t *em, const int32_t *len,
-                     KeyIn *keys);
+// message slot (em, em_slot = the modulus length, 256 or 512 bytes per object) zeroed
+void launch_obj_keys(hipStream_t s, int n, const ObjBlk *ob, ObjState *st, uint8_t *em, int em_slot,
+                     const int32_t *len, KeyIn *keys);
 // launch_load_gate / the verdict half of launch_load_finish with rules 1-4 in
 // front (jfsx_objload.h); opened null with JFSX_CIPHER_NONE, zo null with JFSX_CODEC_NONE
 void launch_obj_gate(hipStream_t s, int n, const LoadBlk *lb, const ObjBlk *ob, const ObjState *st,
@@ -393,22 +393,30 @@ void launch_store_verdict(hipStream_t s, int n, const StoreBlk *sb, const BlkOut
                           StoreRes *res);
 // batched RSA-OAEP unwrap (jfsx_rsa.hip): key = device jfsx_rsa::Key
 void async_detach(jfsx_ctx *c);  // jfsx_agg.cpp
-void launch_rsa_unwrap(hipStream_t s, const void *key, int n, const uint8_t *ct, uint32_t *mh, uint8_t *em,
-                       int32_t *len);
+// kbytes = the modulus length k, 256 (key = jfsx_rsa::Key) or 512 (jfsx_rsa::KeyW):
+// ct and em are n x k bytes, mh is n x rsa_mh_words(k) words of workspace (at
+// 256 the two CRT halves; at 512 the ciphertext as words and the halves as
+// 2 x 76 limbs of 28 bits)
+constexpr size_t rsa_mh_words(int kbytes) { return kbytes == 512 ? 128 + 2 * 76 : 64; }
+void launch_rsa_unwrap(hipStream_t s, const void *key, int kbytes, int n, const uint8_t *ct, uint32_t *mh,
+                       uint8_t *em, int32_t *len);
 // batched RSA-OAEP wrap with public exponent e: item i's message in the
-// kRsaWrapSlot-byte slot i of msg (len[i] bytes; above the OAEP capacity: 256
-// zero bytes out), its seed at seed + 32 i; em = n x 64 words of workspace, ct =
-// n x 256 bytes out (all device memory)
+// rsa_wrap_slot(k)-byte slot i of msg (len[i] bytes; above the OAEP capacity: k
+// zero bytes out), its seed at seed + 32 i; em = n x rsa_em_words(k) words of
+// workspace (EM, and at 512 the result as 4 x 37 limbs of 28 bits over it), ct =
+// n x k bytes out (all device memory)
+constexpr size_t rsa_em_words(int kbytes) { return kbytes == 512 ? 4 * 37 : 64; }
 constexpr int kRsaWrapSlot = 192;
-void launch_rsa_wrap(hipStream_t s, const void *key, uint32_t e, int n, const uint8_t *msg, const uint32_t *len,
-                     const uint8_t *seed, uint32_t *em, uint8_t *ct);
+constexpr int rsa_wrap_slot(int kbytes) { return kbytes == 512 ? 448 : kRsaWrapSlot; }
+void launch_rsa_wrap(hipStream_t s, const void *key, int kbytes, uint32_t e, int n, const uint8_t *msg,
+                     const uint32_t *len, const uint8_t *seed, uint32_t *em, uint8_t *ct);
 // One-call object store (jfsx_objstore.hip): the kernels that put the key wrap
 // in front of jfsx_store_batch's chain and the object's frame behind it.
 // SobjBlk describes one block that reached the Seal (the k-th of m); idx is its
 // place in the batch, where its key's message slot and wrapped key lie.
 struct SobjBlk {
     uint8_t *obj;       // where the object starts, 1 mod 16 (device)
-    uint64_t img_len;   // bytes of C at obj + 271
+    uint64_t img_len;   // bytes of C at obj + 15 + k (271, or 527 with a 4096-bit key)
     uint32_t nonce[3];
     uint32_t idx;
     uint32_t seg_off;   // JFSX_CRC_CT: C's segment CRCs start at this word of the Seal's CRC words
@@ -420,13 +428,13 @@ struct SobjRes {  // copied back to the host
     int32_t status;
 };
 // one thread per block: the 32-byte data key out of slot idx of the wrap's
-// messages (kRsaWrapSlot bytes each) into keys[k].key
-void launch_sobj_keys(hipStream_t s, int m, const SobjBlk *sb, const uint8_t *msg, KeyIn *keys);
-// one wave per block: BE16(256) | 12 | wrapped[idx] | nonce at obj, the tag of
+// messages (rsa_wrap_slot(kbytes) bytes each) into keys[k].key
+void launch_sobj_keys(hipStream_t s, int m, const SobjBlk *sb, const uint8_t *msg, int kbytes, KeyIn *keys);
+// one wave per block: BE16(kbytes) | 12 | wrapped[idx] (kbytes each) | nonce at obj, the tag of
 // sealed[k] behind the image, and with crc_ct CRC32C of the whole object,
 // folded from the header, segs (big-endian segment CRCs) and the tag, into res[k]
-void launch_sobj_frame(hipStream_t s, int m, const SobjBlk *sb, const uint8_t *wrapped, const BlkOut *sealed,
-                       const uint8_t *segs, bool crc_ct, const uint32_t *x8pow, SobjRes *res);
+void launch_sobj_frame(hipStream_t s, int m, const SobjBlk *sb, const uint8_t *wrapped, int kbytes,
+                       const BlkOut *sealed, const uint8_t *segs, bool crc_ct, const uint32_t *x8pow, SobjRes *res);
 // jfsx_gather_batch (jfsx_gather.hip): one launch over the n_tiles tiles of
 // n_pages pages; pages / pieces are jfsx_gather::GPage[n_pages] and its GPiece
 // runs in device memory (jfsx_gather.h).  ncu sizes the grid: 8 workgroups per CU.

@@ -25,7 +25,7 @@ constexpr int kLanes = 64;
 
 // what the host found in a block's header before anything ran (ObjBlk.flags)
 constexpr uint32_t kHdrBad = 1;    // rule 2: hdr_len < 3 or != 3 + klen + nlen
-constexpr uint32_t kKeyBad = 2;    // rule 3: klen == 0 or klen > 256 (rsa.DecryptOAEP's size check)
+constexpr uint32_t kKeyBad = 2;    // rule 3: klen == 0 or klen > k, the modulus length (rsa.DecryptOAEP's size check)
 constexpr uint32_t kNonceBad = 4;  // rule 4: nlen != 12 (aead.Open's nonce size check)
 
 // crc_mulmod / crc_xpow8 of jfsx_internal.h, for both sides

@@ -27,7 +27,6 @@ namespace jfsx {
 namespace {
 
 constexpr int kObjThreads = 256;
-constexpr int kEmSlot = 256;  // bytes of the unwrap's message slot per object (jfsx_rsa::kModBytes)
 
 // One wave per object.
 __global__ __launch_bounds__(64) void obj_fold_k(int n, const ObjBlk *__restrict__ ob, uint32_t tail,
@@ -47,7 +46,7 @@ __global__ __launch_bounds__(64) void obj_fold_k(int n, const ObjBlk *__restrict
 // record reports), not on key bytes.
 __global__ __launch_bounds__(kObjThreads) void obj_keys_k(int n, const ObjBlk *__restrict__ ob,
                                                           ObjState *__restrict__ st, uint8_t *__restrict__ em,
-                                                          const int32_t *__restrict__ len,
+                                                          int em_slot, const int32_t *__restrict__ len,
                                                           KeyIn *__restrict__ keys) {
     const int i = blockIdx.x * kObjThreads + threadIdx.x;
     if (i >= n) return;
@@ -56,12 +55,12 @@ __global__ __launch_bounds__(kObjThreads) void obj_keys_k(int n, const ObjBlk *_
     // rules 1-3 with Open's status left out: what is known before Open runs
     const bool ok = jfsx_obj::early_status(true, st[i].crc_bad != 0, true, flags & ~jfsx_obj::kNonceBad, kl,
                                            JFSX_OK) == JFSX_OK;
-    uint32_t *slot = reinterpret_cast<uint32_t *>(em + (size_t)kEmSlot * i);  // 256-byte aligned
+    // em_slot = the unwrap's message slot per object, the modulus length (256 or 512): 256-byte aligned
+    uint32_t *slot = reinterpret_cast<uint32_t *>(em + (size_t)em_slot * i);
 #pragma unroll
     for (int w = 0; w < 8; w++) keys[i].key[w] = ok ? slot[w] : 0u;
     uint4 *q = reinterpret_cast<uint4 *>(slot);
-#pragma unroll
-    for (int w = 0; w < kEmSlot / 16; w++) q[w] = make_uint4(0, 0, 0, 0);
+    for (int w = 0; w < em_slot / 16; w++) q[w] = make_uint4(0, 0, 0, 0);
     st[i].key_len = kl;
 }
 
@@ -127,11 +126,11 @@ void launch_obj_fold(hipStream_t s, int n, const ObjBlk *ob, uint32_t tail, cons
     if (n > 0) hipLaunchKernelGGL(obj_fold_k, dim3(n), dim3(64), 0, s, n, ob, tail, x8pow, st);
 }
 
-void launch_obj_keys(hipStream_t s, int n, const ObjBlk *ob, ObjState *st, uint8_t *em, const int32_t *len,
-                     KeyIn *keys) {
+void launch_obj_keys(hipStream_t s, int n, const ObjBlk *ob, ObjState *st, uint8_t *em, int em_slot,
+                     const int32_t *len, KeyIn *keys) {
     if (n > 0)
         hipLaunchKernelGGL(obj_keys_k, dim3((n + kObjThreads - 1) / kObjThreads), dim3(kObjThreads), 0, s, n, ob, st,
-                           em, len, keys);
+                           em, em_slot, len, keys);
 }
 
 void launch_obj_gate(hipStream_t s, int n, const LoadBlk *lb, const ObjBlk *ob, const ObjState *st,

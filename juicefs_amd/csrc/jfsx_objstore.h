@@ -6,8 +6,9 @@
 // all three without a GPU.
 //
 // The stored object is dataEncryptor.Encrypt's (pkg/object/encrypt.go:164-194)
-//   BE16(256) | 12 | wrapped key (256) | nonce (12) | C | tag (16)
-// and its checksum generateChecksum's CRC32C of all of it
+//   BE16(k) | 12 | wrapped key (k) | nonce (12) | C | tag (16)
+// with k the modulus length of the volume's RSA key (256, or 512 for a
+// 4096-bit key: the kbytes argument below), and its checksum generateChecksum's CRC32C of all of it
 // (pkg/object/checksum.go:31-53).  The header and the tag exist in device
 // memory only (the wrap's output and the Seal's BlkOut), so their CRCs are
 // computed there: lane l takes the bytes [l * per, (l + 1) * per) of the span,
@@ -26,22 +27,25 @@ constexpr uint32_t kKeyBytes = 256;  // RSA-2048: the wrapped key
 constexpr uint32_t kNonceBytes = 12;
 constexpr uint32_t kHdrBytes = 3 + kKeyBytes + kNonceBytes;  // JFSX_OBJ_HDR_BYTES
 constexpr uint32_t kTagBytes = 16;                           // JFSX_OBJ_TAG_BYTES
+// the header of a key of kbytes: 271, or 527 for RSA-4096
+constexpr uint32_t hdr_bytes(uint32_t kbytes) { return 3 + kbytes + kNonceBytes; }
 
-// byte k < kHdrBytes of the header
-JFSX_HD uint8_t hdr_byte(uint32_t k, const uint8_t *wrapped, const uint8_t *nonce) {
-    if (k < 3) return k == 0 ? (uint8_t)(kKeyBytes >> 8) : k == 1 ? (uint8_t)(kKeyBytes & 255) : (uint8_t)kNonceBytes;
-    return k < 3 + kKeyBytes ? wrapped[k - 3] : nonce[k - 3 - kKeyBytes];
+// byte k < hdr_bytes(kbytes) of the header
+JFSX_HD uint8_t hdr_byte(uint32_t k, const uint8_t *wrapped, const uint8_t *nonce, uint32_t kbytes = kKeyBytes) {
+    if (k < 3) return k == 0 ? (uint8_t)(kbytes >> 8) : k == 1 ? (uint8_t)(kbytes & 255) : (uint8_t)kNonceBytes;
+    return k < 3 + kbytes ? wrapped[k - 3] : nonce[k - 3 - kbytes];
 }
 
 // lane's stores of the frame around C.  obj is 1 mod 16, so the wrapped key at
-// obj + 3 and the nonce at obj + 259 take dword stores (wk is dword aligned);
-// the tag lies wherever the image ends and takes byte stores.
+// obj + 3 and the nonce at obj + 3 + kbytes (259 or 515) take dword stores (wk
+// is dword aligned); the tag lies wherever the image ends and takes byte stores.
 JFSX_HD void frame_store(uint32_t lane, uint8_t *obj, const uint8_t *wk, const uint32_t *nonce, const uint8_t *tag,
-                         uint64_t img_len) {
-    if (lane < 3) obj[lane] = hdr_byte(lane, wk, nullptr);
-    reinterpret_cast<uint32_t *>(obj + 3)[lane] = reinterpret_cast<const uint32_t *>(wk)[lane];
-    if (lane < kNonceBytes / 4) reinterpret_cast<uint32_t *>(obj + 3 + kKeyBytes)[lane] = nonce[lane];
-    if (lane < kTagBytes) obj[kHdrBytes + img_len + lane] = tag[lane];
+                         uint64_t img_len, uint32_t kbytes = kKeyBytes) {
+    if (lane < 3) obj[lane] = hdr_byte(lane, wk, nullptr, kbytes);
+    for (uint32_t w = lane; w < kbytes / 4; w += jfsx_obj::kLanes)
+        reinterpret_cast<uint32_t *>(obj + 3)[w] = reinterpret_cast<const uint32_t *>(wk)[w];
+    if (lane < kNonceBytes / 4) reinterpret_cast<uint32_t *>(obj + 3 + kbytes)[lane] = nonce[lane];
+    if (lane < kTagBytes) obj[hdr_bytes(kbytes) + img_len + lane] = tag[lane];
 }
 
 // crc32.Update(crc, one byte), bit by bit
@@ -63,8 +67,9 @@ JFSX_HD uint32_t span_lane(uint32_t lane, uint32_t len, Get get, const uint32_t 
     return jfsx_obj::mulmod(jfsx_obj::xpow8(len - hi, x8pow), v);
 }
 
-JFSX_HD uint32_t hdr_lane(uint32_t lane, const uint8_t *wrapped, const uint8_t *nonce, const uint32_t *x8pow) {
-    return span_lane(lane, kHdrBytes, [&](uint32_t k) { return hdr_byte(k, wrapped, nonce); }, x8pow);
+JFSX_HD uint32_t hdr_lane(uint32_t lane, const uint8_t *wrapped, const uint8_t *nonce, const uint32_t *x8pow,
+                          uint32_t kbytes = kKeyBytes) {
+    return span_lane(lane, hdr_bytes(kbytes), [&](uint32_t k) { return hdr_byte(k, wrapped, nonce, kbytes); }, x8pow);
 }
 
 JFSX_HD uint32_t bytes_lane(uint32_t lane, const uint8_t *p, uint32_t len, const uint32_t *x8pow) {

@@ -9,6 +9,8 @@
 // m = m2 + h q; then EME-OAEP decoding (RFC 8017 7.1.2) with SHA-256 as hash
 // and MGF1 hash.  Primes are 1024-bit (RSA-2048, the size the reference docs
 // use), in 32 little-endian 32-bit limbs; products use Montgomery CIOS.
+// RSA-4096 (2048-bit primes) is the second and last size: the "RSA-4096"
+// section at the end of this file, pinned by tests/test_rsa4096.py.
 //
 // The write side, rsaEncryptor.Encrypt = rsa.EncryptOAEP (encrypt.go:128-130),
 // is the last part of this file: EME-OAEP encoding and the public operation
@@ -119,8 +121,11 @@ JFSX_HD void ct_add_if(uint32_t *a, const uint32_t *b, int n, uint32_t mask) {
     }
 }
 
-// out = a b R^-1 mod m (R = 2^1024), a, b < m; CIOS with one final subtract
+// out = a b R^-1 mod m (R = 2^(32 NL): 2^1024, or 2^2048 for an RSA-4096
+// prime), a, b < m; CIOS with one final subtract
+template <int NL = kLimbs>
 JFSX_HD void mont_mul(const uint32_t *a, const uint32_t *b, const uint32_t *m, uint32_t minv, uint32_t *out) {
+    constexpr int kLimbs = NL;  // the body below is written on this name
     JFSX_RSA_TRACE('M', 0);
     uint32_t t[kLimbs + 2];
 #pragma unroll
@@ -316,9 +321,10 @@ struct Key {
     uint32_t ninv28;                    // -n^-1 mod 2^28
 };
 
-// 2^bits mod m for an odd m of nl <= 2 kLimbs limbs (mont_r2 at another width)
+// 2^bits mod m for an odd m of nl <= 4 kLimbs limbs (mont_r2 at another width;
+// 4 kLimbs is the n of RSA-4096)
 JFSX_HD void mont_r2_wide(const uint32_t *m, int nl, uint32_t *r2, int bits) {
-    uint32_t x[2 * kLimbs + 1];
+    uint32_t x[4 * kLimbs + 1];
     for (int j = 0; j <= nl; j++) x[j] = 0;
     x[0] = 1;
     for (int k = 0; k < bits; k++) {  // x = 2^k mod m
@@ -381,9 +387,12 @@ JFSX_HD bool key_setup(Key &k, const uint8_t *p, const uint8_t *q, const uint8_t
 }
 
 // c mod m for a 2048-bit c = hi R + lo (hi, lo < R): (hi R mod m) + lo, reduced
+// (NL = 2 kLimbs: the same for a 4096-bit c and a 2048-bit m, R = 2^2048)
+template <int NL = kLimbs>
 JFSX_HD void reduce_2048(const uint32_t *c, const uint32_t *m, uint32_t minv, const uint32_t *r2, uint32_t *out) {
+    constexpr int kLimbs = NL;
     uint32_t t[kLimbs + 1];
-    mont_mul(c + kLimbs, r2, m, minv, t);  // hi R mod m (hi < R, r2 < m: CIOS bound holds)
+    mont_mul<NL>(c + kLimbs, r2, m, minv, t);  // hi R mod m (hi < R, r2 < m: CIOS bound holds)
     t[kLimbs] = add_in(t, c, kLimbs);      // + lo: < 3m since lo < R < 2m
     for (int rep = 0; rep < 2; rep++) {     // two masked corrections, always both
         const uint32_t ge = ct_nz(t[kLimbs]) | ct_geq(t, m, kLimbs);
@@ -393,7 +402,10 @@ JFSX_HD void reduce_2048(const uint32_t *c, const uint32_t *m, uint32_t minv, co
 }
 
 // m = m2 + q (qinv (m1 - m2) mod p), the 2048-bit CRT recombination
-JFSX_HD void crt(const Key &k, const uint32_t *m1, const uint32_t *m2, uint32_t *m) {
+// (NL = 2 kLimbs, K = KeyW: the 4096-bit one)
+template <int NL = kLimbs, class K = Key>
+JFSX_HD void crt(const K &k, const uint32_t *m1, const uint32_t *m2, uint32_t *m) {
+    constexpr int kLimbs = NL;
     uint32_t t[kLimbs + 1], h[kLimbs], u[kLimbs];
     for (int j = 0; j < kLimbs; j++) t[j] = m2[j];
     t[kLimbs] = 0;
@@ -401,8 +413,8 @@ JFSX_HD void crt(const Key &k, const uint32_t *m1, const uint32_t *m2, uint32_t 
     for (int j = 0; j < kLimbs; j++) u[j] = m1[j];
     const uint32_t neg = 0u - sub_in(u, t, kLimbs);     // (m1 - m2) mod p
     ct_add_if(u, k.p, kLimbs, neg);
-    mont_mul(u, k.qinv, k.p, k.pinv, h);               // u qinv R^-1
-    mont_mul(h, k.r2p, k.p, k.pinv, h);                // u qinv
+    mont_mul<NL>(u, k.qinv, k.p, k.pinv, h);           // u qinv R^-1
+    mont_mul<NL>(h, k.r2p, k.p, k.pinv, h);            // u qinv
     for (int j = 0; j < 2 * kLimbs; j++) m[j] = j < kLimbs ? m2[j] : 0;
     for (int i = 0; i < kLimbs; i++) {  // m += h q, carries run to the top every time
         uint64_t c = 0;
@@ -797,13 +809,13 @@ constexpr int kN28 = 74;                               // and in 28-bit limbs (2
 constexpr int kMaxMsg = kModBytes - 2 * kHash - 2;     // OAEP capacity: 190 bytes
 constexpr uint32_t kMinE = 2, kMaxE = 0x7FFFFFFFu;     // Go's checkPub
 
-// EME-OAEP encode (RFC 8017 7.1.1 step 2, Go's EncryptOAEP): em = 00 ‖
-// maskedSeed ‖ maskedDB with DB = lhash ‖ PS ‖ 01 ‖ msg; len <= kMaxMsg.  Only
+// EME-OAEP encode (RFC 8017 7.1.1 step 2, Go's EncryptOAEP): em (k bytes) = 00 ‖
+// maskedSeed ‖ maskedDB with DB = lhash ‖ PS ‖ 01 ‖ msg; len <= k - 66.  Only
 // the length places bytes; the message and seed bytes are moved and hashed.
-JFSX_HD void oaep_encode(const uint8_t lhash[32], const uint8_t *msg, int len, const uint8_t *seed,
-                         uint8_t em[kModBytes]) {
+JFSX_HD void oaep_encode(const uint8_t lhash[32], const uint8_t *msg, int len, const uint8_t *seed, uint8_t *em,
+                         int k = kModBytes) {
     uint8_t *ms = em + 1, *db = em + 1 + kHash;
-    const int dblen = kModBytes - kHash - 1, sep = dblen - 1 - len;
+    const int dblen = k - kHash - 1, sep = dblen - 1 - len;
     em[0] = 0;
     for (int i = 0; i < kHash; i++) db[i] = lhash[i], ms[i] = seed[i];
     for (int i = kHash; i < dblen; i++) db[i] = i < sep ? 0 : i == sep ? 1 : msg[i - sep - 1];
@@ -832,13 +844,36 @@ JFSX_HD void from28_wide(const uint32_t *y, int n28, uint32_t *x, int n32) {
 // out = a b R''^-1 mod m for a 2048-bit odd m: a, b < m in kN28 normalized
 // limbs, minv = -m^-1 mod 2^28; out normalized and < m.  mont_mul28 at twice
 // the width; the accumulator bound is the one stated above.
+//
+// N = kN28W = 148 is the same modulo a 4096-bit m (RSA-4096's n).  There a
+// column would take up to 148 rows of two products, 296 (2^28 - 1)^2 > 2^64:
+// the lazy accumulators alone overflow.  So after kSweepAt = 74 rows the
+// carries are resolved once, in place (every column back below 2^28, plus a
+// carry below 2^37 in the next): no column then holds more than 74 rows' worth
+// before the sweep nor more than 74 rows' worth and 2^38 after it, the bound
+// above.  The sweep moves bits between columns and leaves the value alone, so
+// the reduction multipliers and the result are what they are without it.
+constexpr int kSweepAt = 74;
+constexpr int n32_of(int n28) { return 28 * n28 / 2048 * 64; }  // 32-bit limbs of the modulus: 74 -> 64, 148 -> 128
+constexpr bool needs_sweep(int n28) { return 2 * n28 >= 256; }  // 2 n28 (2^28 - 1)^2 + 2^38 < 2^64 below that
+
+template <int N = 74>
 JFSX_HD void mont_mul28_wide(const uint32_t *a, const uint32_t *b, const uint32_t *m, uint32_t minv, uint32_t *out) {
+    constexpr int kN28 = N;  // the body below is written on this name
     JFSX_RSA_TRACE('M', 3);
     uint64_t acc[kN28];
 #pragma unroll
     for (int j = 0; j < kN28; j++) acc[j] = 0;
 #pragma unroll
     for (int i = 0; i < kN28; i++) {
+        if (needs_sweep(N) && i == kSweepAt) {
+            uint64_t c = 0;
+            for (int j = 0; j < kN28; j++) {
+                c += acc[j];
+                acc[j] = c & kM28;
+                c >>= 28;
+            }  // c == 0: the running value is below 2 m < 2^(28 N)
+        }
         const uint32_t ai = a[i];
 #pragma unroll
         for (int j = 0; j < kN28; j++) acc[j] += (uint64_t)ai * b[j];
@@ -896,9 +931,12 @@ JFSX_HD bool pub_next(PubSchedule &s) {
     return true;
 }
 
-// x^e mod m (x < m, m odd, 2048 bits; 32-bit limbs in and out), kMinE <= e
+// x^e mod m (x < m, m odd, 2048 bits, or 4096 bits for N = kN28W; 32-bit limbs
+// in and out), kMinE <= e
+template <int N = 74>
 JFSX_HD void mod_exp28_pub(const uint32_t *x32, uint32_t e, const uint32_t *m32, uint32_t minv, const uint32_t *r2_32,
                            uint32_t *out32) {
+    constexpr int kN28 = N, kNLimbs = n32_of(N);
     uint32_t m[kN28], xr[kN28], acc[kN28], b[kN28];
     for (int j = 0; j < kN28; j++) {
         m[j] = limb28(m32, kNLimbs, j);
@@ -916,7 +954,7 @@ JFSX_HD void mod_exp28_pub(const uint32_t *x32, uint32_t e, const uint32_t *m32,
         } else if (s.phase == PubSchedule::kLeave) {
             for (int j = 0; j < kN28; j++) b[j] = j == 0;
         }
-        mont_mul28_wide(acc, b, m, minv, acc);
+        mont_mul28_wide<N>(acc, b, m, minv, acc);
         if (s.phase == PubSchedule::kEnter)
             for (int j = 0; j < kN28; j++) xr[j] = acc[j];
     } while (pub_next(s));
@@ -951,11 +989,88 @@ JFSX_HD uint64_t prev64(const X &x, uint64_t v) {
     return (uint64_t)x.prev((uint32_t)v) | (uint64_t)x.prev((uint32_t)(v >> 32)) << 32;
 }
 
-// out = a b R''^-1 mod m on the quad: a, b, m, out are this lane's kQC limbs
-// (normalized, a, b < m); the accumulator bound is mont_mul28_wide's
-template <class X>
+// a compile-time number as an argument (of the generic lambdas below)
+template <int V>
+struct Const {
+    static constexpr int value = V;
+};
+
+// f(Const<I>{}) for I = B .. E - 1, in order
+template <int B, int E, class F>
+JFSX_HD void static_for(F &&f) {
+    if constexpr (B < E) {
+        f(Const<B>{});
+        static_for<B + 1, E>(f);
+    }
+}
+
+// t = the normalized limbs of the value in the quad's QC column accumulators
+// per lane: each lane on its own, then the carry out of lane k - 1 (below
+// 2^37) through lane k, for k = 1, 2, 3
+template <int QC, class X>
+JFSX_HD void quad_normalize(const X &x, const uint64_t *acc, uint32_t *t) {
+    uint64_t c = 0;
+#pragma unroll
+    for (int j = 0; j < QC; j++) {
+        c += acc[j];
+        t[j] = (uint32_t)c & kM28;
+        c >>= 28;
+    }
+#pragma unroll
+    for (uint32_t k = 1; k < 4; k++) {
+        uint64_t ci = prev64(x, c) & ((uint64_t)0 - (uint64_t)(x.lane == k));
+#pragma unroll
+        for (int j = 0; j < QC; j++) {
+            ci += t[j];
+            t[j] = (uint32_t)ci & kM28;
+            ci >>= 28;
+        }
+        c += ci;
+    }
+}
+
+// out = t >= m ? t - m : t on the quad's normalized limbs, by a mask: every
+// lane's borrow out for a borrow in of 0 (g) and of 1 (p), then the chain over
+// the four (g, p) pairs, the same in all lanes
+template <int QC, class X>
+JFSX_HD void quad_sub_if_geq(const X &x, const uint32_t *t, const uint32_t *m, uint32_t *out) {
+    uint32_t d[QC];
+    uint32_t g = 0, p = 1;
+#pragma unroll
+    for (int j = 0; j < QC; j++) {
+        g = (t[j] - m[j] - g) >> 31;
+        p = (t[j] - m[j] - p) >> 31;
+    }
+    uint32_t br = 0, bin = 0;
+    br = x.template from<0>(g) | (x.template from<0>(p) & br);
+    bin |= br & (0u - (uint32_t)(x.lane == 1u));
+    br = x.template from<1>(g) | (x.template from<1>(p) & br);
+    bin |= br & (0u - (uint32_t)(x.lane == 2u));
+    br = x.template from<2>(g) | (x.template from<2>(p) & br);
+    bin |= br & (0u - (uint32_t)(x.lane == 3u));
+    br = x.template from<3>(g) | (x.template from<3>(p) & br);
+#pragma unroll
+    for (int j = 0; j < QC; j++) {
+        const uint32_t v = t[j] - m[j] - bin;
+        d[j] = v & kM28;
+        bin = v >> 31;
+    }
+    const uint32_t keep = 0u - br;  // t < m
+#pragma unroll
+    for (int j = 0; j < QC; j++) out[j] = (t[j] & keep) | (d[j] & ~keep);
+}
+
+// out = a b R''^-1 mod m on the quad: a, b, m, out are this lane's QC = (N +
+// 3) / 4 limbs (normalized, b < m, a < m or at least a < R'' = 2^(28 N): the
+// value before the last subtract is below b + m either way); the accumulator
+// bound is mont_mul28_wide's, and so is the carry sweep at N = kN28W = 4 x 37,
+// which falls between the rows of lane 1 and lane 2 (kSweepAt = 2 QC there)
+// and hands each lane's carry out to the first column of the lane above
+template <class X, int N = 74>
 JFSX_HD void mont_mul28_quad(const X &x, const uint32_t *a, const uint32_t *b, const uint32_t *m, uint32_t minv,
                              uint32_t *out) {
+    constexpr int kN28 = N, kQC = (N + 3) / 4;  // the body below is written on these names
+    static_assert(!needs_sweep(N) || kSweepAt == 2 * kQC, "the sweep sits between two lanes' rows");
     if (x.tracing()) JFSX_RSA_TRACE('M', 4);
     const uint64_t first = (uint64_t)0 - (uint64_t)(x.lane == 0u), inner = (uint64_t)0 - (uint64_t)(x.lane != 3u);
     uint64_t acc[kQC];
@@ -976,68 +1091,65 @@ JFSX_HD void mont_mul28_quad(const X &x, const uint32_t *a, const uint32_t *b, c
         acc[kQC - 1] = s & inner;
         acc[0] += c & first;
     };
+    if constexpr (!needs_sweep(N)) {
+        // 74 rows, all unrolled: the shifts are register renaming
 #pragma unroll
-    for (int r = 0; r < kQC; r++) row(x.template from<0>(a[r]));
+        for (int r = 0; r < kQC; r++) row(x.template from<0>(a[r]));
 #pragma unroll
-    for (int r = 0; r < kQC; r++) row(x.template from<1>(a[r]));
+        for (int r = 0; r < kQC; r++) row(x.template from<1>(a[r]));
 #pragma unroll
-    for (int r = 0; r < kQC; r++) row(x.template from<2>(a[r]));
+        for (int r = 0; r < kQC; r++) row(x.template from<2>(a[r]));
 #pragma unroll
-    for (int r = 0; r < kN28 - 3 * kQC; r++) row(x.template from<3>(a[r]));
-    // normalize: each lane on its own, then the carry out of lane k - 1
-    // (below 2^37) through lane k, for k = 1, 2, 3
-    uint32_t t[kQC], d[kQC];
-    uint64_t c = 0;
+        for (int r = 0; r < kN28 - 3 * kQC; r++) row(x.template from<3>(a[r]));
+    } else {
+        // 148 rows of 74 multiply-adds unrolled would be several times the
+        // instruction cache: a loop over the four lanes' rows instead, one
+        // lane's 37 rows unrolled in its body.  A row's limb of a comes from
+        // lane 0 every time: after a lane's rows every lane takes over the
+        // limbs of the lane above it (all indices static: an indexed read
+        // would put a into scratch memory), and over 37 rows every column has
+        // moved down by one whole lane, into the registers it started from.
+        static_assert(N == 4 * kQC, "whole lanes of rows");
+        uint32_t ar[kQC];
 #pragma unroll
-    for (int j = 0; j < kQC; j++) {
-        c += acc[j];
-        t[j] = (uint32_t)c & kM28;
-        c >>= 28;
-    }
+        for (int j = 0; j < kQC; j++) ar[j] = a[j];
+#pragma unroll 1
+        for (int g = 0; g < 4; g++) {
+            if (g == 2) {
+                // the carry sweep; lane 3's carry out is zero: the running
+                // value is below 2 m, and m ends inside lane 3's columns
+                uint64_t c = 0;
 #pragma unroll
-    for (uint32_t k = 1; k < 4; k++) {
-        uint64_t ci = prev64(x, c) & ((uint64_t)0 - (uint64_t)(x.lane == k));
+                for (int j = 0; j < kQC; j++) {
+                    c += acc[j];
+                    acc[j] = c & kM28;
+                    c >>= 28;
+                }
+                acc[0] += prev64(x, c) & ~first;
+            }
+            // (unrolled by the template: 37 rows are past what the
+            // compiler unrolls on a pragma's word)
+            static_for<0, kQC>([&](auto r) { row(x.template from<0>(ar[decltype(r)::value])); });
 #pragma unroll
-        for (int j = 0; j < kQC; j++) {
-            ci += t[j];
-            t[j] = (uint32_t)ci & kM28;
-            ci >>= 28;
+            for (int r = 0; r < kQC; r++) ar[r] = x.next(ar[r]);
         }
-        c += ci;
     }
-    // t - m: every lane's borrow out for a borrow in of 0 (g) and of 1 (p),
-    // then the chain over the four (g, p) pairs, the same in all lanes
-    uint32_t g = 0, p = 1;
-#pragma unroll
-    for (int j = 0; j < kQC; j++) {
-        g = (t[j] - m[j] - g) >> 31;
-        p = (t[j] - m[j] - p) >> 31;
-    }
-    uint32_t br = 0, bin = 0;
-    br = x.template from<0>(g) | (x.template from<0>(p) & br);
-    bin |= br & (0u - (uint32_t)(x.lane == 1u));
-    br = x.template from<1>(g) | (x.template from<1>(p) & br);
-    bin |= br & (0u - (uint32_t)(x.lane == 2u));
-    br = x.template from<2>(g) | (x.template from<2>(p) & br);
-    bin |= br & (0u - (uint32_t)(x.lane == 3u));
-    br = x.template from<3>(g) | (x.template from<3>(p) & br);
-#pragma unroll
-    for (int j = 0; j < kQC; j++) {
-        const uint32_t v = t[j] - m[j] - bin;
-        d[j] = v & kM28;
-        bin = v >> 31;
-    }
-    const uint32_t keep = 0u - br;  // t < m
-#pragma unroll
-    for (int j = 0; j < kQC; j++) out[j] = (t[j] & keep) | (d[j] & ~keep);
+    uint32_t t[kQC];
+    quad_normalize<kQC>(x, acc, t);
+    quad_sub_if_geq<kQC>(x, t, m, out);
 }
 
-// x^e mod m on the quad (x < m; 32-bit limbs in, out32 in all four lanes):
-// mod_exp28_pub's schedule
-template <class X>
-JFSX_HD void mod_exp28_pub_quad(const X &x, const uint32_t *x32, uint32_t e, const uint32_t *m32, uint32_t minv,
-                                const uint32_t *r2_32, uint32_t *out32) {
-    uint32_t m[kQC], xr[kQC], acc[kQC], b[kQC];
+// x^e mod m on the quad (x < m; 32-bit limbs in, this lane's kQC normalized
+// 28-bit limbs of the result out): mod_exp28_pub's schedule.  With park (kQC
+// words of memory of this lane's own) x R'' waits there between the product
+// that makes it and the multiplies that take it, not in registers: at 37
+// columns the registers do not hold it next to acc, the operand, m and the
+// column accumulators.  The addresses are the lane's, whatever the data.
+template <class X, int N = 74>
+JFSX_HD void mod_exp28_pub_quad_lane(const X &x, const uint32_t *x32, uint32_t e, const uint32_t *m32, uint32_t minv,
+                                     const uint32_t *r2_32, uint32_t *acc, uint32_t *park = nullptr) {
+    constexpr int kQC = (N + 3) / 4, kNLimbs = n32_of(N);  // 74: 19, 64; kN28W: 37, 128
+    uint32_t m[kQC], xr[kQC], b[kQC];
     const uint32_t one0 = x.lane == 0u;  // the Montgomery 1's low limb sits in lane 0
 #pragma unroll
     for (int j = 0; j < kQC; j++) {
@@ -1055,17 +1167,29 @@ JFSX_HD void mod_exp28_pub_quad(const X &x, const uint32_t *x32, uint32_t e, con
             for (int j = 0; j < kQC; j++) b[j] = acc[j];
         } else if (s.phase == PubSchedule::kMultiply) {
 #pragma unroll
-            for (int j = 0; j < kQC; j++) b[j] = xr[j];
+            for (int j = 0; j < kQC; j++) b[j] = park ? park[j] : xr[j];
         } else if (s.phase == PubSchedule::kLeave) {
 #pragma unroll
             for (int j = 0; j < kQC; j++) b[j] = j == 0 ? one0 : 0u;
         }
-        mont_mul28_quad(x, acc, b, m, minv, acc);
+        mont_mul28_quad<X, N>(x, acc, b, m, minv, acc);
         if (s.phase == PubSchedule::kEnter) {
 #pragma unroll
-            for (int j = 0; j < kQC; j++) xr[j] = acc[j];
+            for (int j = 0; j < kQC; j++) {
+                if (park) park[j] = acc[j];
+                else xr[j] = acc[j];
+            }
         }
     } while (pub_next(s));
+}
+
+// the same with the whole result in every lane, as 32-bit limbs
+template <class X, int N = 74>
+JFSX_HD void mod_exp28_pub_quad(const X &x, const uint32_t *x32, uint32_t e, const uint32_t *m32, uint32_t minv,
+                                const uint32_t *r2_32, uint32_t *out32) {
+    constexpr int kN28 = N, kQC = (N + 3) / 4, kNLimbs = n32_of(N);
+    uint32_t acc[kQC];
+    mod_exp28_pub_quad_lane<X, N>(x, x32, e, m32, minv, r2_32, acc);
     // all four quarters of the result in every lane, back to 32-bit limbs
     uint32_t f[4 * kQC];
 #pragma unroll
@@ -1094,6 +1218,261 @@ JFSX_HD int encrypt(const Key &k, uint32_t e, const uint8_t *msg, int len, const
     from_be(em, kModBytes, x, kNLimbs);
     mod_exp28_pub(x, e, k.n, k.ninv28, k.r2n28, r);
     to_be(r, kNLimbs, ct, kModBytes);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// RSA-4096: the second and last key size (`juicefs format --encrypt-rsa-key`
+// with a 4096-bit key; 3072-bit and every other size stay refused).  k = 512
+// bytes, the primes are 2048 bits: 64 limbs of 32 bits, kN28 = 74 limbs of 28,
+// which is the width the wrap's quad product already has, so a CRT half is a
+// fixed-window exponentiation over mont_mul28_quad<X, 74> with the 8-entry
+// table in registers.  n is 128 limbs of 32 bits, kN28W = 148 of 28, 37
+// columns per lane of the quad (mont_mul28_quad<X, 148>, with the carry sweep).
+// The CRT recombination and the one-lane pins run the 32-bit CIOS at 64 limbs.
+// ---------------------------------------------------------------------------
+constexpr int kLimbsW = 2 * kLimbs;                      // 2048-bit prime
+constexpr int kNLimbsW = 2 * kLimbsW;                    // 4096-bit n
+constexpr int kModBytesW = 4 * kNLimbsW;                 // 512
+// n in 28-bit limbs: 147 hold it (4116 bits); 148 = 4 x 37 are taken, the top
+// one always zero, so that every lane of the quad has 37 whole columns and the
+// product 37 whole rows per lane (R'' = 2^(28 * 148))
+constexpr int kN28W = 148;
+constexpr int kQCW = (kN28W + 3) / 4;                    // 37 columns per lane
+constexpr int kMaxMsgW = kModBytesW - 2 * kHash - 2;     // OAEP capacity: 446 bytes
+constexpr int kWDigitsW = (32 * kLimbsW + kWBits - 1) / kWBits;  // 683 window digits
+constexpr int kHalfBits = 32 * kLimbsW;                  // the input reduction splits c = hi 2^2048 + lo
+
+struct KeyW {
+    uint32_t n[kNLimbsW];
+    uint32_t p[kLimbsW], q[kLimbsW];
+    uint32_t dp[kLimbsW], dq[kLimbsW];
+    uint32_t qinv[kLimbsW];
+    uint32_t r2p[kLimbsW], r2q[kLimbsW];      // 2^4096 mod p, q: the 32-bit CIOS (CRT, one-lane reduction)
+    uint32_t r2p28[kLimbsW], r2q28[kLimbsW];  // R'^2 mod p, q, R' = 2^(28 kN28): the exponentiation
+    uint32_t rxp[kLimbsW], rxq[kLimbsW];      // 2^2048 R' mod p, q: the quad's input reduction
+    uint32_t pinv, qinv32;                    // -p^-1, -q^-1 mod 2^32
+    int32_t dp_bits, dq_bits;
+    uint8_t lhash[32];
+    uint32_t r2n28[kNLimbsW];                 // R''^2 mod n, R'' = 2^(28 kN28W)
+    uint32_t ninv28;                          // -n^-1 mod 2^28
+};
+
+// KeyW from the CRT components (big-endian, 256 bytes each): key_setup's
+// checks at this width (odd primes with bit 2047 set, dp, dq >= 2)
+JFSX_HD bool key_setup_w(KeyW &k, const uint8_t *p, const uint8_t *q, const uint8_t *dp, const uint8_t *dq,
+                         const uint8_t *qinv, const uint8_t *label, int label_len) {
+    constexpr int L = kLimbsW, nb = 4 * L;
+    from_be(p, nb, k.p, L);
+    from_be(q, nb, k.q, L);
+    from_be(dp, nb, k.dp, L);
+    from_be(dq, nb, k.dq, L);
+    from_be(qinv, nb, k.qinv, L);
+    if (!(k.p[0] & 1u) || !(k.q[0] & 1u) || bit_length(k.p, L) != 32 * L || bit_length(k.q, L) != 32 * L) return false;
+    k.dp_bits = bit_length(k.dp, L);
+    k.dq_bits = bit_length(k.dq, L);
+    if (k.dp_bits < 2 || k.dq_bits < 2) return false;
+    k.pinv = mont_inv32(k.p[0]);
+    k.qinv32 = mont_inv32(k.q[0]);
+    mont_r2_wide(k.p, L, k.r2p, 2 * 32 * L);
+    mont_r2_wide(k.q, L, k.r2q, 2 * 32 * L);
+    mont_r2_wide(k.p, L, k.r2p28, 2 * 28 * kN28);
+    mont_r2_wide(k.q, L, k.r2q28, 2 * 28 * kN28);
+    mont_r2_wide(k.p, L, k.rxp, kHalfBits + 28 * kN28);
+    mont_r2_wide(k.q, L, k.rxq, kHalfBits + 28 * kN28);
+    for (int j = 0; j < 2 * L; j++) k.n[j] = 0;
+    for (int i = 0; i < L; i++) {
+        uint64_t c = 0;
+        for (int j = 0; j < L; j++) {
+            c = (uint64_t)k.p[i] * k.q[j] + (c + k.n[i + j]);
+            k.n[i + j] = (uint32_t)c;
+            c >>= 32;
+        }
+        k.n[i + L] = (uint32_t)c;
+    }
+    sha256_2(label, label_len, label, 0, k.lhash);
+    mont_r2_wide(k.n, kNLimbsW, k.r2n28, 2 * 28 * kN28W);
+    k.ninv28 = mont_inv32(k.n[0]) & kM28;
+    return true;
+}
+
+// digit d (0 = least significant) of the nl-limb e in kWBits-bit digits
+JFSX_HD uint32_t w_digit_n(const uint32_t *e, int nl, int d) {
+    const int b = kWBits * d, l = b >> 5, o = b & 31;
+    uint64_t v = e[l];
+    if (l + 1 < nl) v |= (uint64_t)e[l + 1] << 32;
+    return (uint32_t)(v >> o) & (kWTab - 1);
+}
+
+// x^e mod m for a 2048-bit m and a 2048-bit e on ONE lane (x < m; 32-bit limbs
+// in and out): mod_exp28 over mont_mul28_wide.  The CPU pin of the whole
+// unwrap runs it; on the GPU its table would not fit the registers, and the
+// kernel runs the quad form below.
+JFSX_HD void mod_exp28_priv_wide(const uint32_t *x32, const uint32_t *e, const uint32_t *m32, uint32_t minv32,
+                                 const uint32_t *r2_32, uint32_t *out32) {
+    constexpr int L = kN28;
+    uint32_t m[L], x[L], r2[L];
+    for (int j = 0; j < L; j++)
+        m[j] = limb28(m32, kLimbsW, j), x[j] = limb28(x32, kLimbsW, j), r2[j] = limb28(r2_32, kLimbsW, j);
+    const uint32_t minv = minv32 & kM28;
+    uint32_t tab[kWTab][L];
+    uint32_t acc[L], b[L];
+    for (int w = 0; w < kWTab; w++)
+        for (int j = 0; j < L; j++) tab[w][j] = 0;
+    constexpr int kPer = kWBits + 1, kMain = kWTab + kPer * kWDigitsW;
+#pragma unroll 1
+    for (int st = 0; st <= kMain; st++) {
+        if (st == 0) {
+            for (int j = 0; j < L; j++) acc[j] = r2[j], b[j] = j == 0;
+        } else if (st == 1) {
+            for (int j = 0; j < L; j++) acc[j] = x[j], b[j] = r2[j];
+        } else if (st < kWTab) {
+            for (int j = 0; j < L; j++) b[j] = tab[1][j];
+        } else if (st < kMain) {
+            const int r = st - kWTab;
+            if (r % kPer < kWBits) {
+                for (int j = 0; j < L; j++) b[j] = acc[j];
+            } else {
+                uint32_t idx = w_digit_n(e, kLimbsW, kWDigitsW - 1 - r / kPer);
+                JFSX_RSA_OPAQUE(idx);
+                for (int j = 0; j < L; j++) b[j] = 0;
+                for (uint32_t w = 0; w < (uint32_t)kWTab; w++) {
+                    uint32_t msk = ~ct_nz(w ^ idx);
+                    JFSX_RSA_OPAQUE(msk);
+                    JFSX_RSA_TRACE('S', w);
+                    for (int j = 0; j < L; j++) b[j] |= tab[w][j] & msk;
+                }
+            }
+        } else {
+            for (int j = 0; j < L; j++) b[j] = j == 0;
+        }
+        mont_mul28_wide(acc, b, m, minv, acc);
+        if (st < kWTab) {
+            for (int j = 0; j < L; j++) tab[st][j] = acc[j];
+            if (st == kWTab - 1)
+                for (int j = 0; j < L; j++) acc[j] = tab[0][j];
+        }
+    }
+    from28_wide(acc, L, out32, kLimbsW);
+}
+
+// ---------------------------------------------------------------------------
+// The private half on a QUAD of lanes (the GPU kernel's form): everything is
+// this lane's kQC = 19 limbs of a 74-limb value, as in mont_mul28_quad.
+//
+// The input reduction c mod m for the 4096-bit c = hi 2^2048 + lo and the
+// 2048-bit m runs through the quad product, not through a 64-limb one-lane
+// CIOS: t = hi rx R'^-1 = hi 2^2048 mod m with rx = 2^2048 R' mod m from the
+// key (hi < 2^2048 < R', rx < m: the product's bound holds), then t + lo < 3 m
+// (lo < 2^2048 < 2 m), carried across the lanes, and two masked subtractions
+// of m, always both: reduce_2048's steps.
+// ---------------------------------------------------------------------------
+template <class X>
+JFSX_HD void reduce_quad(const X &x, const uint32_t *hi, const uint32_t *lo, const uint32_t *m, uint32_t minv,
+                         const uint32_t *rx, uint32_t *out) {
+    uint32_t t[kQC];
+    mont_mul28_quad(x, hi, rx, m, minv, t);
+    uint64_t s[kQC];
+#pragma unroll
+    for (int j = 0; j < kQC; j++) s[j] = (uint64_t)t[j] + lo[j];
+    quad_normalize<kQC>(x, s, t);  // < 3 m < 2^2050: inside the 74 limbs
+    quad_sub_if_geq<kQC>(x, t, m, t);
+    quad_sub_if_geq<kQC>(x, t, m, out);
+}
+
+// out = xv^e mod m on the quad (xv < m; e a 2048-bit exponent in 64 32-bit
+// limbs, the same pointer in all lanes; r2 = R'^2 mod m), constant time in e:
+// mod_exp28_pair's schedule -- one multiply site in a loop over a step
+// counter, table writes at static indices, every digit multiplies, the entry
+// picked by a masked scan of all 8 behind a register barrier -- with the
+// 8 x 19 table in this lane's registers.
+template <class X>
+JFSX_HD void mod_exp28_priv_quad(const X &x, const uint32_t *xv, const uint32_t *e, const uint32_t *m, uint32_t minv,
+                                 const uint32_t *r2, uint32_t *out) {
+    const uint32_t one0 = x.lane == 0u;  // the Montgomery 1's low limb sits in lane 0
+    uint32_t tab[kWTab][kQC];
+    uint32_t acc[kQC], b[kQC];
+    for (int w = 0; w < kWTab; w++)
+        for (int j = 0; j < kQC; j++) tab[w][j] = 0;
+    constexpr int kPer = kWBits + 1, kMain = kWTab + kPer * kWDigitsW;
+#pragma unroll 1
+    for (int st = 0; st <= kMain; st++) {
+        if (st == 0) {  // R' mod m = r2 * 1
+#pragma unroll
+            for (int j = 0; j < kQC; j++) acc[j] = r2[j], b[j] = j == 0 ? one0 : 0u;
+        } else if (st == 1) {  // x R' mod m
+#pragma unroll
+            for (int j = 0; j < kQC; j++) acc[j] = xv[j], b[j] = r2[j];
+        } else if (st < kWTab) {  // tab[st] = tab[st - 1] * x R'
+#pragma unroll
+            for (int j = 0; j < kQC; j++) b[j] = tab[1][j];
+        } else if (st < kMain) {
+            const int r = st - kWTab;
+            if (r % kPer < kWBits) {
+#pragma unroll
+                for (int j = 0; j < kQC; j++) b[j] = acc[j];
+            } else {
+                uint32_t idx = w_digit_n(e, kLimbsW, kWDigitsW - 1 - r / kPer);
+                JFSX_RSA_OPAQUE(idx);
+#pragma unroll
+                for (int j = 0; j < kQC; j++) b[j] = 0;
+#pragma unroll
+                for (uint32_t w = 0; w < (uint32_t)kWTab; w++) {
+                    uint32_t msk = ~ct_nz(w ^ idx);
+                    JFSX_RSA_OPAQUE(msk);
+                    if (x.tracing()) JFSX_RSA_TRACE('S', w);
+#pragma unroll
+                    for (int j = 0; j < kQC; j++) b[j] |= tab[w][j] & msk;
+                }
+            }
+        } else {  // out of the Montgomery domain
+#pragma unroll
+            for (int j = 0; j < kQC; j++) b[j] = j == 0 ? one0 : 0u;
+        }
+        mont_mul28_quad(x, acc, b, m, minv, acc);
+        if (st < kWTab) {
+#pragma unroll
+            for (int w = 0; w < kWTab; w++)
+#pragma unroll
+                for (int j = 0; j < kQC; j++) tab[w][j] = st == w ? acc[j] : tab[w][j];
+            if (st == kWTab - 1) {
+#pragma unroll
+                for (int j = 0; j < kQC; j++) acc[j] = tab[0][j];
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < kQC; j++) out[j] = acc[j];
+}
+
+// One whole 4096-bit unwrap on one thread (the CPU pin): ct = 512 bytes,
+// big-endian.  Returns the message length (msg in em[0..len)) or -1.
+JFSX_HD int decrypt_w(const KeyW &k, const uint8_t *ct, uint8_t em[kModBytesW]) {
+    uint32_t c[kNLimbsW], m1[kLimbsW], m2[kLimbsW], m[kNLimbsW], x[kLimbsW];
+    from_be(ct, kModBytesW, c, kNLimbsW);
+    if (geq(c, k.n, kNLimbsW)) return -1;
+    reduce_2048<kLimbsW>(c, k.p, k.pinv, k.r2p, x);
+    mod_exp28_priv_wide(x, k.dp, k.p, k.pinv, k.r2p28, m1);
+    reduce_2048<kLimbsW>(c, k.q, k.qinv32, k.r2q, x);
+    mod_exp28_priv_wide(x, k.dq, k.q, k.qinv32, k.r2q28, m2);
+    crt<kLimbsW>(k, m1, m2, m);
+    to_be(m, kNLimbsW, em, kModBytesW);
+    return oaep_decode(em, kModBytesW, k.lhash);
+}
+
+// One whole 4096-bit wrap on one thread (the CPU pin): encrypt() at k = 512
+JFSX_HD int encrypt_w(const KeyW &k, uint32_t e, const uint8_t *msg, int len, const uint8_t *seed,
+                      uint8_t ct[kModBytesW]) {
+    if (len < 0 || len > kMaxMsgW) {
+        for (int i = 0; i < kModBytesW; i++) ct[i] = 0;
+        return -1;
+    }
+    uint8_t em[kModBytesW];
+    oaep_encode(k.lhash, msg, len, seed, em, kModBytesW);
+    uint32_t x[kNLimbsW], r[kNLimbsW];
+    from_be(em, kModBytesW, x, kNLimbsW);
+    mod_exp28_pub<kN28W>(x, e, k.n, k.ninv28, k.r2n28, r);
+    to_be(r, kNLimbsW, ct, kModBytesW);
     return 0;
 }
 

@@ -246,8 +246,9 @@ class RsaEncryptor:
         """Decrypt for a whole read window at once: the engine's batched
         RSA-OAEP unwrap on the GPU, bit-exact to
         rsa.DecryptOAEP.  Returns, per item, the plaintext or the EncryptError
-        Decrypt would raise.  Keys the engine does not take (not RSA-2048)
-        unwrap on the host as the reference does (encrypt.go:132-134)."""
+        Decrypt would raise.  The engine takes RSA-2048 and RSA-4096 keys;
+        any other size (3072 bits, ...) unwraps on the host as the reference
+        does (encrypt.go:132-134)."""
         eng = eng or default_engine()
         dk = self._device_key(eng)
         if dk is None:
@@ -265,11 +266,11 @@ class RsaEncryptor:
         """Encrypt for a whole upload window at once: the engine's batched
         RSA-OAEP wrap on the GPU with the key's public exponent, one 32-byte
         OAEP seed per item from rand (what rsa.EncryptOAEP reads from its
-        random source), in order.  Returns, per item, the 256-byte ciphertext
-        or the EncryptError Encrypt would raise.  Keys the engine does not
-        take (not RSA-2048, or e outside 2 .. 2^31 - 1) wrap on the host one
-        by one, as the reference does (encrypt.go:128-130); rand is then not
-        read."""
+        random source), in order.  Returns, per item, the ciphertext (as long
+        as the modulus) or the EncryptError Encrypt would raise.  Keys the
+        engine does not take (neither RSA-2048 nor RSA-4096, or e outside 2 ..
+        2^31 - 1) wrap on the host one by one, as the reference does
+        (encrypt.go:128-130); rand is then not read."""
         eng = eng or default_engine()
         dk = self._device_key(eng)
         e = rsa_public_exponent(self.privKey) if dk is not None else 0
@@ -290,8 +291,10 @@ class RsaEncryptor:
         keys = self.__dict__.setdefault("_dev_keys", {})
         if eng.ctx not in keys:
             try:
-                keys[eng.ctx] = eng.rsa_key(*rsa_crt_components(self.privKey), label=self.label)
-            except Exception:  # not RSA-2048 with CRT parameters
+                # the engine checks the size: half the modulus length per component
+                comps = rsa_crt_components(self.privKey, self.privKey.size // 2)
+                keys[eng.ctx] = eng.rsa_key(*comps, label=self.label)
+            except Exception:  # neither RSA-2048 nor RSA-4096 with CRT parameters
                 keys[eng.ctx] = None
         return keys[eng.ctx]
 

@@ -45,7 +45,7 @@ EXPORTS = [
     "jfsx_seal_batch", "jfsx_open_batch", "jfsx_crc32c_segments", "jfsx_checksum", "jfsx_cache_verify",
     "jfsx_data_encrypt", "jfsx_data_decrypt", "jfsx_parse_header", "jfsx_gen_synthetic", "jfsx_gen_key",
     "jfsx_debug_tables", "jfsx_crc32c_update", "jfsx_crc32c_combine", "jfsx_object_crc32c",
-    "jfsx_rsa_key_new", "jfsx_rsa_key_free", "jfsx_rsa_oaep_decrypt_batch", "jfsx_rsa_oaep_encrypt_batch",
+    "jfsx_rsa_key_new", "jfsx_rsa_key_free", "jfsx_rsa_key_bytes", "jfsx_rsa_oaep_decrypt_batch", "jfsx_rsa_oaep_encrypt_batch",
     "jfsx_seal_batch_async", "jfsx_open_batch_async", "jfsx_crc32c_segments_async", "jfsx_wait",
     "jfsx_agg_new", "jfsx_agg_free", "jfsx_agg_seal", "jfsx_agg_open", "jfsx_agg_crc32c", "jfsx_agg_stats",
     "jfsx_gen_synthetic_batch", "jfsx_mctx_open", "jfsx_mctx_close", "jfsx_mctx_ndev", "jfsx_mctx_ctx",
@@ -59,7 +59,7 @@ EXPORTS = [
     "jfsx_agg_data_encrypt", "jfsx_agg_data_decrypt",
     "jfsx_data_encrypt_ex", "jfsx_data_decrypt_ex", "jfsx_agg_data_encrypt_ex", "jfsx_agg_data_decrypt_ex",
     "jfsx_file_checksum_span", "jfsx_file_checksum_batch", "jfsx_file_checksum_fold",
-    "jfsx_load_batch", "jfsx_store_batch", "jfsx_load_objects", "jfsx_object_bound", "jfsx_store_objects",
+    "jfsx_load_batch", "jfsx_store_batch", "jfsx_load_objects", "jfsx_object_bound", "jfsx_object_bound_key", "jfsx_store_objects",
     "jfsx_compact_plan", "jfsx_gather_batch", "jfsx_compact_objects",
 ]
 
@@ -269,6 +269,7 @@ def load_library(path=LIB_PATH):
             "jfsx_debug_tables": (I, [P, P, P]),
             "jfsx_rsa_key_new": (I, [P, P, P, P, P, P, I, P, I, PP]),
             "jfsx_rsa_key_free": (I, [P]),
+            "jfsx_rsa_key_bytes": (I, [P]),
             "jfsx_rsa_oaep_decrypt_batch": (I, [P, P, I, P, U64, P, P, U64, P]),
             "jfsx_rsa_oaep_encrypt_batch": (I, [P, P, U32, I, P, U64, P, P, P, U64, P]),
             "jfsx_seal_batch_async": (I, [P, I, I, ctypes.POINTER(jfsx_blk), I, I, ctypes.POINTER(U64)]),
@@ -309,6 +310,7 @@ def load_library(path=LIB_PATH):
             "jfsx_store_batch": (I, [P, I, I, I, ctypes.POINTER(jfsx_sblk), I, I]),
             "jfsx_load_objects": (I, [P, P, I, I, I, ctypes.POINTER(jfsx_oblk), I, I]),
             "jfsx_object_bound": (U64, [I, U64]),
+            "jfsx_object_bound_key": (U64, [P, I, U64]),
             "jfsx_store_objects": (I, [P, P, U32, I, I, I, ctypes.POINTER(jfsx_soblk), I, I]),
             "jfsx_compact_plan": (I, [U32, I, ctypes.POINTER(jfsx_slice), I, ctypes.POINTER(jfsx_csrc),
                                       ctypes.POINTER(I), I, ctypes.POINTER(jfsx_cpage), ctypes.POINTER(U64),
@@ -420,13 +422,21 @@ def zstd_bound(n):
     return load_library().jfsx_zstd_bound(n)
 
 
-OBJ_HDR_BYTES = 271  # BE16(256) | 12 | wrapped key | nonce
+OBJ_HDR_BYTES = 271  # BE16(256) | 12 | wrapped key | nonce: an RSA-2048 volume's (527 with a 4096-bit key)
 OBJ_TAG_BYTES = 16
 
 
-def object_bound(codec, n):
-    """Capacity jfsx_store_objects needs for the object of an n-byte page."""
-    return int(load_library().jfsx_object_bound(codec, n))
+def object_bound(codec, n, key=None):
+    """Capacity jfsx_store_objects needs for the object of an n-byte page:
+    under key (rsa_key()'s handle), or an RSA-2048 volume's without one."""
+    if key is None:
+        return int(load_library().jfsx_object_bound(codec, n))
+    return int(load_library().jfsx_object_bound_key(key, codec, n))
+
+
+def rsa_key_bytes(key):
+    """The modulus length of rsa_key()'s handle: 256 or 512."""
+    return int(load_library().jfsx_rsa_key_bytes(key))
 
 
 def make_pieces(pieces):
@@ -945,7 +955,7 @@ class Engine:
         specs, keep = [], []
         for i, (dk, seed, nonce, page) in enumerate(items):
             src = _u8(page)
-            cap = object_bound(codec, src.size)
+            cap = object_bound(codec, src.size, key)
             obj = np.empty(cap, np.uint8)
             if verify is not None:
                 cbuf = _u8(verify[i])
@@ -1025,7 +1035,7 @@ class Engine:
         pages = list(pages)
         sspecs, outs = [], []
         for (dk, seed, nonce), (_, _, n) in zip(draws, pages):
-            cap = object_bound(codec, n)
+            cap = object_bound(codec, n, key)
             obj = np.empty(cap, np.uint8)
             cbuf = np.empty(4 * max(1, -(-int(n) // SEG)), np.uint8)
             outs.append((obj, cbuf))
@@ -1165,8 +1175,9 @@ class Engine:
         return (rc, pt, segs.tobytes()) if seg_crc else (rc, pt)
 
     def rsa_key(self, p, q, dp, dq, qinv, label=b"keys"):
-        """Device copy of an RSA-2048 private key from its CRT components
-        (big-endian, 128 bytes each) for oaep_decrypt_batch."""
+        """Device copy of an RSA-2048 or RSA-4096 private key from its CRT
+        components (big-endian, 128 or 256 bytes each) for the batch calls and
+        the one-call object paths.  Any other size raises (JFSX_EINVAL)."""
         k = ctypes.c_void_p()
         lab = bytes(label)
         self._check(self.L.jfsx_rsa_key_new(self.ctx, bytes(p), bytes(q), bytes(dp), bytes(dq), bytes(qinv), len(p),
@@ -1190,17 +1201,19 @@ class Engine:
             c = bytes(c)
             buf[i * stride:i * stride + len(c)] = np.frombuffer(c, np.uint8)
             lens[i] = len(c)
-        msg = np.zeros(n * 256, np.uint8)
+        k = rsa_key_bytes(key)
+        msg = np.zeros(n * k, np.uint8)
         mlen = np.zeros(n, np.int32)
         self._check(self.L.jfsx_rsa_oaep_decrypt_batch(self.ctx, key, n, buf.ctypes.data, stride, lens.ctypes.data,
-                                                       msg.ctypes.data, 256, mlen.ctypes.data),
+                                                       msg.ctypes.data, k, mlen.ctypes.data),
                     "jfsx_rsa_oaep_decrypt_batch")
-        return [None if mlen[i] < 0 else msg[256 * i:256 * i + mlen[i]].tobytes() for i in range(n)]
+        return [None if mlen[i] < 0 else msg[k * i:k * i + mlen[i]].tobytes() for i in range(n)]
 
     def oaep_encrypt_batch(self, key, msgs, seeds, e=65537):
         """rsa.EncryptOAEP(sha256, rand, pub, m, label) for every m at once,
         with the 32 bytes Go would read from rand given per item (seeds) and
-        the public exponent e: a list of 256-byte ciphertexts, None where Go
+        the public exponent e: a list of ciphertexts as long as the modulus
+        (256 or 512 bytes), None where Go
         returns "message too long for RSA key size"."""
         n = len(msgs)
         if len(seeds) != n or any(len(s) != 32 for s in seeds):
@@ -1215,12 +1228,13 @@ class Engine:
             buf[i * stride:i * stride + len(m)] = np.frombuffer(m, np.uint8)
             lens[i] = len(m)
         sd = np.frombuffer(b"".join(bytes(s) for s in seeds), np.uint8)
-        ct = np.zeros(n * 256, np.uint8)
+        k = rsa_key_bytes(key)
+        ct = np.zeros(n * k, np.uint8)
         st = np.zeros(n, np.int32)
         self._check(self.L.jfsx_rsa_oaep_encrypt_batch(self.ctx, key, e, n, buf.ctypes.data, stride, lens.ctypes.data,
-                                                       sd.ctypes.data, ct.ctypes.data, 256, st.ctypes.data),
+                                                       sd.ctypes.data, ct.ctypes.data, k, st.ctypes.data),
                     "jfsx_rsa_oaep_encrypt_batch")
-        return [None if st[i] < 0 else ct[256 * i:256 * i + 256].tobytes() for i in range(n)]
+        return [None if st[i] < 0 else ct[k * i:k * i + k].tobytes() for i in range(n)]
 
     def crc32c_update(self, crc, data):
         return crc32c_update(crc, data)
