@@ -13,6 +13,8 @@
  *                        + checksum()/verify of the plaintext       pkg/chunk/disk_cache.go:1219, :1315-1327
  *   jfsx_data_encrypt    dataEncryptor.Encrypt (object format)      pkg/object/encrypt.go:164-194
  *   jfsx_data_decrypt    dataEncryptor.Decrypt (object format)      pkg/object/encrypt.go:196-216
+ *   jfsx_open_range_batch encrypted.Get(key, off, limit): the tag   pkg/object/encrypt.go:232-255
+ *                        over all of C, the window alone decrypted  (issued at pkg/chunk/cached_store.go:152-183)
  *   jfsx_checksum        checksum(data) []byte                      pkg/chunk/disk_cache.go:1218-1231
  *   jfsx_crc32c_segments the CRC loop of cacheFile.ReadAt           pkg/chunk/disk_cache.go:1315-1327
  *   jfsx_file_checksum_batch getFileChecksum (MD5-of-MD5-of-CRC32C)  sdk/java/.../JuiceFileSystemImpl.java:1286-1343
@@ -443,6 +445,61 @@ int jfsx_data_encrypt_ex(jfsx_ctx *ctx, int algo, const uint8_t key[32], const u
 int jfsx_data_decrypt_ex(jfsx_ctx *ctx, int algo, const uint8_t key[32], const void *obj, uint64_t olen,
                          void *out, uint64_t out_cap, uint64_t *out_len, const uint32_t *expect_crc,
                          uint32_t *got_crc, uint8_t *seg_crc);
+
+/* Ranged Open -- encrypted.Get(key, off, limit) (pkg/object/encrypt.go:232-255),
+ * the read rSlice.ReadAt issues for a small read that misses the cache on an
+ * encrypted, uncompressed volume (pkg/chunk/cached_store.go:152-183).  The tag
+ * is checked over all of C, the keystream runs only under the window, and only
+ * the window is released.  The window is Go's slice rule (encrypt.go:246-253):
+ *   o = min(off, len);  n = (limit == -1 || limit > len - o) ? len - o : limit
+ * Per block: the tag is always checked, for n == 0 and len == 0 too (Go
+ * decrypts before it slices).  JFSX_OK: out_len = n and dst[0, n) holds the
+ * plaintext bytes [o, o + n), the bytes jfsx_open_batch writes at dst + o.
+ * JFSX_ETAG: out_len = 0 and dst[0, n) is zero.  No byte of dst at or past n
+ * is written; with n == 0 dst may be NULL and is not touched.
+ * crc_mode: JFSX_CRC_NONE, or JFSX_CRC_GEN | JFSX_CRC_CT, which fills crc
+ * with what jfsx_open_batch returns in that mode (the ciphertext segment CRCs
+ * of all of C, on a good tag and on a bad one).  The plaintext outside the
+ * window is never formed, so the plaintext CRC modes are JFSX_EINVAL.
+ * JFSX_EINVAL before anything runs, with the records untouched: an unknown
+ * algo, any other crc_mode, reserved or reserved2 non-zero, limit < -1, len
+ * beyond the cipher's limit (jfsx_blk), dst_cap < n, a NULL dst with n > 0, a
+ * NULL crc with GEN | CT, a NULL src with len > 0; with JFSX_MEM_DEVICE also
+ * src, dst or crc not 16-byte aligned, or dst[0, dst_cap) overlapping
+ * src[0, len).  off and limit have no alignment rule.  Blocks with n == 0 and
+ * a batch of no blocks are legal.
+ * JFSX_MEM_HOST: pageable or pinned memory at any alignment; C goes up once
+ * and exactly n bytes come down, only for a block whose tag verified.  The
+ * call is synchronous and single-buffered.
+ * Metrics: a returned batch counts as open_batches / open_blocks; open_bytes
+ * grows by len, the bytes authenticated; open_fail counts per JFSX_ETAG. */
+typedef struct jfsx_rblk {
+    uint8_t key[32];      /* data key                                         */
+    uint8_t nonce[12];    /* nonce                                            */
+    uint32_t reserved;    /* must be 0                                        */
+    uint8_t tag[16];      /* in                                               */
+    const void *src;      /* C, the whole ciphertext without header and tag   */
+    uint64_t len;         /* bytes of C = bytes of the plaintext              */
+    uint64_t off;         /* encrypted.Get's off                              */
+    int64_t limit;        /* encrypted.Get's limit; -1: to the end            */
+    void *dst;            /* receives the window only                         */
+    uint64_t dst_cap;
+    uint8_t *crc;         /* GEN|CT: out, 4*max(1,ceil(len/32K)) B            */
+    uint64_t out_len;     /* out                                              */
+    int32_t status;       /* out: JFSX_OK / JFSX_ETAG                         */
+    int32_t reserved2;    /* must be 0                                        */
+} jfsx_rblk;
+int jfsx_open_range_batch(jfsx_ctx *ctx, int algo, int n, jfsx_rblk *blks, int crc_mode, int mem);
+/* one more aggregator op: requests with the same (algo, crc_mode, mem)
+ * coalesce into jfsx_open_range_batch calls, with jfsx_agg_open's semantics
+ * (a request the engine rejects fails alone) */
+int jfsx_agg_open_range(jfsx_agg *agg, int algo, jfsx_rblk *blk, int crc_mode, int mem);
+/* jfsx_data_decrypt with the window: the same header parsing and
+ * JFSX_EMISFORMED, JFSX_ECRC before JFSX_ETAG when expect_crc is given;
+ * *out_len = n on success, out_cap >= n; nothing is released on any failure */
+int jfsx_data_decrypt_range(jfsx_ctx *ctx, int algo, const uint8_t key[32], const void *obj, uint64_t olen,
+                            uint64_t off, int64_t limit, void *out, uint64_t out_cap, uint64_t *out_len,
+                            const uint32_t *expect_crc, uint32_t *got_crc);
 
 /* crc32.Update(crc, MakeTable(Castagnoli), data) on the host (small spans:
  * object header and tag) */

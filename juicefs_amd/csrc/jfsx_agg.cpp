@@ -171,7 +171,13 @@ int jfsx_wait(jfsx_ctx *c, jfsx_ticket t, int timeout_ms) {
 
 namespace jfsx {
 
-enum AggOp { kSeal = 0, kOpen = 1, kCrc = 2, kLz4c = 3, kLz4d = 4, kZstdd = 5, kZstdc = 6 };
+enum AggOp { kSeal = 0, kOpen = 1, kCrc = 2, kLz4c = 3, kLz4d = 4, kZstdd = 5, kZstdc = 6, kExt = 7 };
+
+// kExt: an op whose batch call lives outside this file (agg_submit_ext).  The
+// request carries its record (item_size bytes) and the batch entry point, which
+// takes n such records side by side; requests with the same entry point, algo,
+// mode and mem coalesce, and a batch the engine rejects is retried one by one.
+typedef int (*AggBatchFn)(jfsx_ctx *c, int algo, int n, void *items, int mode, int mem);
 
 struct Req {
     int op, algo, mode, mem;
@@ -181,13 +187,18 @@ struct Req {
     uint64_t bytes;
     Clock::time_point t0;
     int rc = 0;
+    void *item = nullptr;  // kExt
+    size_t item_size = 0;
+    AggBatchFn fn = nullptr;
     // completion: each caller sleeps on its own condition variable, so a
     // finished batch wakes only its own callers (not every waiting caller,
     // which would contend on the queue lock the dispatchers need)
     std::mutex m;
     std::condition_variable cv;
     bool fin = false;
-    bool same(const Req &o) const { return op == o.op && algo == o.algo && mode == o.mode && mem == o.mem; }
+    bool same(const Req &o) const {
+        return op == o.op && algo == o.algo && mode == o.mode && mem == o.mem && fn == o.fn;
+    }
 };
 
 }  // namespace jfsx
@@ -276,6 +287,17 @@ struct jfsx_agg {
         std::vector<jfsx_range> rng;
         std::vector<jfsx_zblk> zs;
         const int op = b[0]->op;
+        if (op == jfsx::kExt) {
+            const Req &h = *b[0];
+            const size_t sz = h.item_size;
+            std::vector<char> items(n * sz);
+            for (size_t i = 0; i < n; i++) memcpy(items.data() + i * sz, b[i]->item, sz);
+            const int rc = h.fn(c, h.algo, (int)n, items.data(), h.mode, h.mem);
+            for (size_t i = 0; i < n; i++)
+                b[i]->rc = rc == JFSX_EINVAL && n > 1 ? h.fn(c, h.algo, 1, items.data() + i * sz, h.mode, h.mem) : rc;
+            for (size_t i = 0; i < n; i++) memcpy(b[i]->item, items.data() + i * sz, sz);
+            return;
+        }
         if (op == kCrc) {
             rng.resize(n);
             for (size_t i = 0; i < n; i++) rng[i] = *b[i]->range;
@@ -610,6 +632,20 @@ int jfsx_agg_zstd_compress(jfsx_agg *a, jfsx_zblk *z, int mem) {
 }
 
 }  // extern "C"
+
+namespace jfsx {
+// one request of an op defined elsewhere (jfsx_agg_open_range, jfsx_api.cpp):
+// blocks the caller until its record has been through fn in some batch
+int agg_submit_ext(jfsx_agg *a, AggBatchFn fn, int algo, int mode, int mem, void *item, size_t item_size,
+                   uint64_t bytes) {
+    if (!a || !fn || !item || !item_size || !agg_mem_ok(a, mem)) return JFSX_EINVAL;
+    Req r{kExt, algo, mode, mem, nullptr, nullptr, nullptr, bytes};
+    r.item = item;
+    r.item_size = item_size;
+    r.fn = fn;
+    return a->submit(r);
+}
+}  // namespace jfsx
 
 namespace {
 int agg_aead(jfsx_agg *a, int op, int algo, jfsx_blk *blk, int crc_mode, int mem) {

@@ -486,6 +486,12 @@ struct jfsx_ctx {
     size_t gat_scap = 0;
     char *cmp_d = nullptr;
     size_t cmp_dcap = 0;
+    // jfsx_open_range_batch on host memory: the pinned staging of the callers'
+    // pageable C on its way up and of the windows on their way down (grow-only;
+    // the call holds mu throughout, so one buffer serves).  Its descriptors and
+    // device staging are ws[0]'s.
+    char *rng_h = nullptr;
+    size_t rng_hcap = 0;
     double ms_total = 0;
     uint64_t launches = 0;
     BouncePool bounce;       // pinned staging of pageable caller memory (host calls)
@@ -2801,6 +2807,7 @@ int jfsx_ctx_close(jfsx_ctx *c) {
     if (c->gat_stage) (void)hipFree(c->gat_stage);
     if (c->cmp_d) (void)hipFree(c->cmp_d);
     if (c->gat_h) (void)hipHostFree(c->gat_h);
+    if (c->rng_h) (void)hipHostFree(c->rng_h);
     for (auto &kv : c->bounce.idle) {
         forget_pinned(kv.second);
         (void)hipHostFree(kv.second);
@@ -5230,4 +5237,514 @@ extern "C" int jfsx_compact_objects(jfsx_ctx *c, const jfsx_rsa_key *key, uint32
     CtxScope es_(c);
     HIP_OK(hipSetDevice(c->device));
     return run_compact(c, key, e, algo, codec, n_src, src, src_crc_mode, n_dst, dst, pages, dst_crc_mode, pieces);
+}
+
+// ---------------------------------------------------------------------------
+// Ranged Open: jfsx_open_range_batch, jfsx_data_decrypt_range
+// ---------------------------------------------------------------------------
+namespace {
+
+// Go's slice rule (encrypt.go:246-253) and the window widened to whole
+// segments: [w0, w1) is empty when n == 0
+struct RangeWin {
+    uint64_t o, n, w0, w1;
+};
+RangeWin range_window(uint64_t len, uint64_t off, int64_t limit) {
+    RangeWin r;
+    r.o = std::min(off, len);
+    r.n = (limit == -1 || (uint64_t)limit > len - r.o) ? len - r.o : (uint64_t)limit;
+    r.w0 = r.w1 = 0;
+    if (r.n) {
+        r.w0 = r.o / kSeg * kSeg;
+        r.w1 = std::min(len, (r.o + r.n + kSeg - 1) / kSeg * kSeg);
+    }
+    return r;
+}
+
+// The task lists of a ranged batch.  The widened windows go to the main
+// kernel as ordinary Open tasks, cut by plan_batch as a batch of blocks of the
+// windows' lengths would be; every other segment goes to the auth kernel in
+// tasks of auth_bytes.  A block's slots are contiguous: its main tasks' first,
+// then its auth tasks'.
+//   auth_bytes: a power of two of segments, the largest up to the kernel's
+//   maximum that still leaves `want` tasks in the batch, else its minimum
+//     GCM     64 KiB .. 1 MiB, 512 tasks (one 16-wave workgroup per CU: 4 to 64
+//             rows per wave, and the task's GHASH table built once per task)
+//     ChaCha  32 KiB .. 1 MiB, 2048 tasks (eight 4-wave workgroups per CU: 2 to
+//             64 rows per wave)
+struct RangePlan {
+    std::vector<RangeWin> win;
+    std::vector<Task> main, auth;  // plan order: block by block, c0 ascending
+    std::vector<uint32_t> slot0, nslots, n_main, n_auth;  // per block
+    uint64_t total_slots = 0, main_bytes = 0, auth_bytes = 0;
+    uint32_t max_slots = 0;
+};
+constexpr uint64_t kGcmAuthMin = 2 * (uint64_t)kSeg, kGcmAuthMax = (uint64_t)1 << 20, kGcmAuthWant = 512;
+constexpr uint64_t kCpAuthMin = (uint64_t)kSeg, kCpAuthMax = (uint64_t)1 << 20, kCpAuthWant = 2048;
+
+RangePlan plan_range(bool gcm, int n, const uint64_t *lens, const uint64_t *offs, const int64_t *limits) {
+    RangePlan p;
+    p.win.resize(n);
+    p.slot0.assign(n, 0);
+    p.nslots.assign(n, 0);
+    p.n_main.assign(n, 0);
+    p.n_auth.assign(n, 0);
+    std::vector<uint64_t> wl(n);
+    uint64_t outside = 0;
+    for (int i = 0; i < n; i++) {
+        p.win[i] = range_window(lens[i], offs[i], limits[i]);
+        wl[i] = p.win[i].w1 - p.win[i].w0;
+        outside += lens[i] - wl[i];
+    }
+    const Plan mp = plan_batch(gcm ? kPlanGcm : kPlanCp, wl);
+    p.main_bytes = mp.task_bytes;
+    const uint64_t amin = gcm ? kGcmAuthMin : kCpAuthMin, amax = gcm ? kGcmAuthMax : kCpAuthMax;
+    const uint64_t want = gcm ? kGcmAuthWant : kCpAuthWant;
+    uint64_t ab = amax;
+    while (ab > amin && outside / ab < want) ab >>= 1;
+    p.auth_bytes = ab;
+    const uint32_t mslots = gcm ? kSlotsPerTask : kCpWaves, aslots = gcm ? kGcmAuthWaves : kCpAuthWaves;
+    size_t mt = 0;
+    for (int i = 0; i < n; i++) {
+        const RangeWin &w = p.win[i];
+        p.slot0[i] = (uint32_t)p.total_slots;
+        for (; mt < mp.tasks.size() && mp.tasks[mt].blk == (uint32_t)i; mt++) {
+            Task t = mp.tasks[mt];
+            t.c0 += w.w0;
+            t.c1 += w.w0;
+            t.slot0 = (uint32_t)p.total_slots;
+            p.main.push_back(t);
+            p.total_slots += mslots;
+            p.n_main[i]++;
+        }
+        const uint64_t runs[2][2] = {{0, w.w0}, {w.w1, lens[i]}};
+        for (const auto &r : runs)
+            for (uint64_t c0 = r[0]; c0 < r[1]; c0 += ab) {
+                p.auth.push_back(Task{(uint32_t)i, (uint32_t)p.total_slots, c0, std::min(c0 + ab, r[1])});
+                p.total_slots += aslots;
+                p.n_auth[i]++;
+            }
+        p.nslots[i] = (uint32_t)(p.total_slots - p.slot0[i]);
+        p.max_slots = std::max(p.max_slots, p.nslots[i]);
+    }
+    return p;
+}
+
+bool range_mode_ok(int crc_mode) { return crc_mode == JFSX_CRC_NONE || crc_mode == (JFSX_CRC_GEN | JFSX_CRC_CT); }
+
+// the argument rules of jfsx_open_range_batch; touches neither context nor records
+int check_range_args(int algo, int n, const jfsx_rblk *blks, int crc_mode, int mem) {
+    if (algo != JFSX_AES256GCM && algo != JFSX_CHACHA20P1305) return JFSX_EINVAL;
+    if (!range_mode_ok(crc_mode) || n < 0 || (n > 0 && !blks)) return JFSX_EINVAL;
+    if (mem != JFSX_MEM_HOST && mem != JFSX_MEM_DEVICE) return JFSX_EINVAL;
+    const bool device = mem == JFSX_MEM_DEVICE;
+    for (int i = 0; i < n; i++) {
+        const jfsx_rblk &b = blks[i];
+        if (b.reserved || b.reserved2 || b.limit < -1) return JFSX_EINVAL;
+        if (b.len > (algo == JFSX_AES256GCM ? kGcmMaxLen : kCpMaxLen)) return JFSX_EINVAL;
+        const RangeWin w = range_window(b.len, b.off, b.limit);
+        if (b.dst_cap < w.n || (w.n && !b.dst) || (b.len && !b.src) || (crc_mode && !b.crc)) return JFSX_EINVAL;
+        if (!device) continue;
+        if ((b.len && !aligned16(b.src)) || (w.n && !aligned16(b.dst)) || (crc_mode && !aligned16(b.crc)))
+            return JFSX_EINVAL;
+        if (w.n && b.len) {
+            const uintptr_t s0 = (uintptr_t)b.src, d0 = (uintptr_t)b.dst;
+            if (d0 < s0 + b.len && s0 < d0 + b.dst_cap) return JFSX_EINVAL;
+        }
+    }
+    return 0;
+}
+
+// Under c->mu; every argument has been checked.  One synchronous chain on
+// c->stream in the buffers of the synchronous paths (ws[0], its staging, the
+// gather's descriptors):
+//   host: C up once (pageable blocks through the context's pinned staging)
+//   keysetup | [CT pass] | auth kernel | main kernel into the staging | finalize
+//   BlkOut (and the CRC words of a host call) down, wait
+//   the windows of the blocks that verified gathered out of the staging:
+//     device: into dst (gather_pages_k writes nothing outside [dst, dst + n))
+//     host:   packed, one copy down of exactly their bytes, wait, into dst
+//   a failed block's dst[0, n) zeroed
+int run_open_range(jfsx_ctx *c, int algo, int n, jfsx_rblk *blks, int crc_mode, bool host) {
+    const bool gcm = algo == JFSX_AES256GCM;
+    hipStream_t s = c->stream;
+    Workspace &w = c->ws[0];
+    std::vector<uint64_t> lens(n), offs(n);
+    std::vector<int64_t> lims(n);
+    for (int i = 0; i < n; i++) lens[i] = blks[i].len, offs[i] = blks[i].off, lims[i] = blks[i].limit;
+    const RangePlan rp = plan_range(gcm, n, lens.data(), offs.data(), lims.data());
+    Plan cplan;
+    if (crc_mode) cplan = plan_batch(kPlanCrc, lens);
+    const size_t nmt = rp.main.size(), nat = rp.auth.size(), nct = cplan.tasks.size();
+    // staging: [C of a host call] [the widened windows] [the packed windows of a host call]
+    std::vector<size_t> soff(n), woff(n), poff(n);
+    size_t src_bytes = 0, win_bytes = 0, out_bytes = 0;
+    uint64_t crc_words = 0;
+    for (int i = 0; i < n; i++) {
+        soff[i] = src_bytes;
+        if (host) src_bytes += align256(lens[i]);
+        woff[i] = win_bytes;
+        win_bytes += align256(rp.win[i].w1 - rp.win[i].w0);
+        poff[i] = out_bytes;
+        if (host) out_bytes += align256(rp.win[i].n);
+        crc_words += nseg_of(lens[i]);
+    }
+    int rc;
+    if ((rc = ensure_dev(c, &w.stage, &w.scap, src_bytes + win_bytes + out_bytes))) return rc;
+    char *const st_src = w.stage, *const st_win = w.stage + src_bytes, *const st_out = st_win + win_bytes;
+    // descriptors
+    size_t off = 0;
+    const size_t o_keys = off; off = align256(off + sizeof(KeyIn) * n);
+    const size_t o_blk = off; off = align256(off + sizeof(BlkDev) * n);
+    const size_t o_mtask = off; off = align256(off + sizeof(Task) * std::max<size_t>(nmt, 1));
+    const size_t o_atask = off; off = align256(off + sizeof(Task) * std::max<size_t>(nat, 1));
+    const size_t o_tagin = off; off = align256(off + 16 * (size_t)n);
+    const size_t o_queue = off; off = align256(off + 4);
+    const size_t o_cblk = off; if (crc_mode) off = align256(off + sizeof(BlkDev) * n);
+    const size_t o_ctask = off; if (crc_mode) off = align256(off + sizeof(Task) * std::max<size_t>(nct, 1));
+    const size_t h_bytes = off;
+    const size_t o_out = off; off = align256(off + sizeof(BlkOut) * n);
+    const size_t o_crcout = off; if (crc_mode && host) off = align256(off + 4 * crc_words);
+    const size_t down = crc_mode && host ? o_crcout + 4 * crc_words - o_out : sizeof(BlkOut) * n;
+    const size_t o_sched = off; off = align256(off + (gcm ? sizeof(GcmSched) : sizeof(CpSched)) * n);
+    const size_t o_part = off; off = align256(off + 32 * std::max<uint64_t>(rp.total_slots, 1));
+    const size_t o_pexp = off; off = align256(off + 4 * std::max<uint64_t>(rp.total_slots, 1));
+    if ((rc = ensure_dev(c, &w.d, &w.dcap, off))) return rc;
+    if ((rc = ensure_host(&w.h, &w.hcap, std::max(h_bytes, down)))) return rc;
+    char *h = w.h, *d = w.d;
+    KeyIn *hk = (KeyIn *)(h + o_keys);
+    BlkDev *hb = (BlkDev *)(h + o_blk);
+    *(uint32_t *)(h + o_queue) = 0;
+    uint64_t cw = 0;
+    for (int i = 0; i < n; i++) {
+        const jfsx_rblk &b = blks[i];
+        memcpy(hk[i].key, b.key, 32);
+        memcpy(hk[i].nonce, b.nonce, 12);
+        hk[i].pad = 0;
+        memset(&hb[i], 0, sizeof(BlkDev));
+        hb[i].src = host ? (const uint8_t *)st_src + soff[i] : (const uint8_t *)b.src;
+        // the main kernel writes plaintext byte k of the block at dst + k: the
+        // window's first segment lands at the start of the block's staging
+        hb[i].dst = (uint8_t *)((uintptr_t)(st_win + woff[i]) - (uintptr_t)rp.win[i].w0);
+        hb[i].len = b.len;
+        hb[i].slot0 = rp.slot0[i];
+        hb[i].nslots = rp.nslots[i];
+        hb[i].tag_in = (const uint8_t *)(d + o_tagin + 16 * (size_t)i);
+        memcpy(h + o_tagin + 16 * (size_t)i, b.tag, 16);
+        if (crc_mode) {
+            BlkDev &cb = ((BlkDev *)(h + o_cblk))[i];
+            memset(&cb, 0, sizeof(cb));
+            cb.src = hb[i].src;
+            cb.len = b.len;
+            cb.crc = host ? (uint8_t *)(d + o_crcout + 4 * cw) : b.crc;
+        }
+        cw += nseg_of(b.len);
+    }
+    if (nmt) {
+        memcpy(h + o_mtask, rp.main.data(), sizeof(Task) * nmt);
+        order_largest_first((Task *)(h + o_mtask), nmt, (size_t)(gcm ? kMaxTaskBytes : kCpTaskBytes) >> 12);
+    }
+    if (nat) {
+        memcpy(h + o_atask, rp.auth.data(), sizeof(Task) * nat);
+        order_largest_first((Task *)(h + o_atask), nat, (size_t)rp.auth_bytes >> 12);
+    }
+    cplan.dispatch((Task *)(h + o_ctask));
+
+    // host: the blocks' C into the staging
+    char *bounce = nullptr;
+    std::vector<char> in_b(n, 0);
+    bool all_in = host, any_in = false;
+    if (host) {
+        for (int i = 0; i < n; i++) {
+            if (!lens[i]) continue;
+            in_b[i] = !host_pinned(blks[i].src, lens[i]);
+            all_in = all_in && in_b[i];
+            any_in = any_in || in_b[i];
+        }
+        const size_t need = std::max(any_in ? src_bytes : 0, out_bytes);
+        if (need && (rc = ensure_host(&c->rng_h, &c->rng_hcap, need))) return rc;
+        bounce = c->rng_h;
+        std::vector<std::pair<char *, const char *>> cp;
+        std::vector<size_t> cl;
+        for (int i = 0; i < n; i++)
+            if (in_b[i]) {
+                cp.push_back({bounce + soff[i], (const char *)blks[i].src});
+                cl.push_back(lens[i]);
+            }
+        par_copy(cp, cl);
+    }
+    const BlkDev *db = (const BlkDev *)(d + o_blk);
+    uint32_t *dpart = (uint32_t *)(d + o_part), *dpexp = (uint32_t *)(d + o_pexp);
+    const bool timed = c->timing && (nmt || nat);
+    const auto chain = [&]() {
+        if (host && all_in && src_bytes) {
+            HIP_OK(hipMemcpyAsync(st_src, bounce, src_bytes, hipMemcpyHostToDevice, s));
+        } else if (host) {
+            for (int i = 0; i < n; i++)
+                if (lens[i])
+                    HIP_OK(hipMemcpyAsync(st_src + soff[i], in_b[i] ? bounce + soff[i] : (const char *)blks[i].src,
+                                          lens[i], hipMemcpyHostToDevice, s));
+        }
+        HIP_OK(hipMemcpyAsync(d, h, h_bytes, hipMemcpyHostToDevice, s));
+        launch_begin();
+        if (gcm) launch_gcm_keysetup(s, n, (const KeyIn *)(d + o_keys), db, (GcmSched *)(d + o_sched), c->tabs, c->bitslice);
+        else launch_cp_keysetup(s, n, (const KeyIn *)(d + o_keys), db, (CpSched *)(d + o_sched));
+        if (crc_mode) {
+            for (int i = 0; i < n; i++)  // checksum() of nothing: one zero word
+                if (lens[i] == 0) HIP_OK(hipMemsetAsync(((const BlkDev *)(h + o_cblk))[i].crc, 0, 4, s));
+            launch_crc_segments(s, (int)nct, (const Task *)(d + o_ctask), (const BlkDev *)(d + o_cblk), c->tabs);
+        }
+        if (timed) HIP_OK(hipEventRecord(c->ev_k0[0], s));
+        if (gcm) {
+            launch_gcm_auth(s, (int)nat, (const Task *)(d + o_atask), db, (const GcmSched *)(d + o_sched), dpart, dpexp);
+            launch_gcm_main(s, (int)nmt, c->ncu, (uint32_t *)(d + o_queue), true, JFSX_CRC_NONE, c->bitslice,
+                            (const Task *)(d + o_mtask), db, (const GcmSched *)(d + o_sched), dpart, dpexp, c->tabs,
+                            c->crc_l1);
+        } else {
+            launch_cp_auth(s, (int)nat, (const Task *)(d + o_atask), db, (const CpSched *)(d + o_sched), dpart, dpexp);
+            launch_cp_main(s, (int)nmt, c->ncu, (uint32_t *)(d + o_queue), true, JFSX_CRC_NONE,
+                           (const Task *)(d + o_mtask), db, (const CpSched *)(d + o_sched), dpart, dpexp, c->tabs);
+        }
+        if (timed) HIP_OK(hipEventRecord(c->ev_k1[0], s));
+        if (gcm)
+            launch_gcm_finalize(s, n, true, JFSX_CRC_NONE, db, (const GcmSched *)(d + o_sched), dpart, dpexp,
+                                (BlkOut *)(d + o_out), rp.max_slots);
+        else
+            launch_cp_finalize(s, n, true, JFSX_CRC_NONE, db, (const CpSched *)(d + o_sched), dpart, dpexp,
+                               (BlkOut *)(d + o_out));
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpyAsync(h, d + o_out, down, hipMemcpyDeviceToHost, s));
+        return 0;
+    };
+    // the stream is waited for whatever the enqueue returned, so a failure leaves nothing in flight
+    const auto settle = [&](int r, const char *what) {
+        const hipError_t se = hipStreamSynchronize(s);
+        if (!r && se != hipSuccess) {
+            note_hip_error(se, __FILE__, __LINE__, what);
+            r = JFSX_EIO;
+        }
+        return r;
+    };
+    rc = settle(chain(), "hipStreamSynchronize(open_range)");
+    if (!rc && timed) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, c->ev_k0[0], c->ev_k1[0]) == hipSuccess) add_kernel_ms(c, ms);
+        else (void)hipGetLastError();
+    }
+    if (rc) return rc;
+    // the windows of the blocks that verified, out of the staging
+    const BlkOut *ho = (const BlkOut *)h;
+    std::vector<const uint8_t *> sp(n, nullptr);
+    std::vector<uint8_t *> dp(n, nullptr);
+    std::vector<uint64_t> dlen(n, 0);
+    std::vector<GatherRun> runs(n);
+    std::vector<jfsx_piece> pieces(n);
+    for (int i = 0; i < n; i++) {
+        const RangeWin &rw = rp.win[i];
+        runs[i] = GatherRun{(uint32_t)i, 1};
+        pieces[i] = jfsx_piece{i, 0, 0, rw.n};
+        if (ho[i].status != JFSX_OK || !rw.n) continue;
+        sp[i] = (const uint8_t *)st_win + woff[i] + (rw.o - rw.w0);
+        dp[i] = host ? (uint8_t *)st_out + poff[i] : (uint8_t *)blks[i].dst;
+        dlen[i] = rw.n;
+    }
+    const auto place = [&]() {
+        const int r = gather_enqueue(c, sp.data(), n, dp.data(), dlen.data(), runs.data(), pieces.data(), false);
+        if (r) return r;
+        if (host) {
+            // exactly the windows' bytes: runs of verified blocks that lie back to back in the packed buffer
+            for (int i = 0; i < n;) {
+                if (!dlen[i]) {
+                    i++;
+                    continue;
+                }
+                int j = i;
+                while (j + 1 < n && dlen[j + 1] && poff[j] + dlen[j] == poff[j + 1]) j++;
+                const size_t bytes = poff[j] + dlen[j] - poff[i];
+                HIP_OK(hipMemcpyAsync(bounce + poff[i], st_out + poff[i], bytes, hipMemcpyDeviceToHost, s));
+                i = j + 1;
+            }
+        } else {
+            for (int i = 0; i < n; i++)
+                if (ho[i].status != JFSX_OK && rp.win[i].n) HIP_OK(hipMemsetAsync(blks[i].dst, 0, rp.win[i].n, s));
+        }
+        return 0;
+    };
+    rc = settle(place(), "hipStreamSynchronize(open_range windows)");
+    if (!rc) {
+        if (host) {
+            std::vector<std::pair<char *, const char *>> cp;
+            std::vector<size_t> cl;
+            for (int i = 0; i < n; i++) {
+                if (dlen[i]) {
+                    cp.push_back({(char *)blks[i].dst, bounce + poff[i]});
+                    cl.push_back(dlen[i]);
+                } else if (rp.win[i].n) {
+                    memset(blks[i].dst, 0, rp.win[i].n);
+                }
+            }
+            par_copy(cp, cl);
+            if (crc_mode) {
+                const char *hw = h + (o_crcout - o_out);
+                for (int i = 0; i < n; i++) {
+                    memcpy(blks[i].crc, hw, 4 * nseg_of(lens[i]));
+                    hw += 4 * nseg_of(lens[i]);
+                }
+            }
+        }
+        for (int i = 0; i < n; i++) {
+            blks[i].status = ho[i].status;
+            blks[i].out_len = ho[i].status == JFSX_OK ? rp.win[i].n : 0;
+        }
+    }
+    return rc;
+}
+
+}  // namespace
+
+extern "C" int jfsx_open_range_batch(jfsx_ctx *c, int algo, int n, jfsx_rblk *blks, int crc_mode, int mem) {
+    if (!c) return JFSX_EINVAL;
+    int rc = check_range_args(algo, n, blks, crc_mode, mem);
+    if (rc || n == 0) return rc;
+    {
+        std::lock_guard<std::mutex> g(c->mu);
+        CtxScope es_(c);
+        HIP_OK(hipSetDevice(c->device));
+        rc = run_open_range(c, algo, n, blks, crc_mode, mem == JFSX_MEM_HOST);
+    }
+    if (rc == 0) {
+        std::lock_guard<std::mutex> g(c->stat_mu);
+        jfsx_metrics &m = c->met;
+        m.open_batches++;
+        m.open_blocks += n;
+        for (int i = 0; i < n; i++) {
+            m.open_bytes += blks[i].len;
+            m.open_fail += blks[i].status != JFSX_OK;
+        }
+    }
+    return rc;
+}
+
+namespace {
+using RangeFn = std::function<int(jfsx_rblk *, int crc_mode)>;
+
+// data_decrypt with the window
+int data_decrypt_range(const RangeFn &open, const uint8_t key[32], const void *obj, uint64_t olen, uint64_t off,
+                       int64_t limit, void *out, uint64_t out_cap, uint64_t *out_len, const uint32_t *expect_crc,
+                       uint32_t *got_crc) {
+    if (!key || !obj || limit < -1) return JFSX_EINVAL;
+    int kl = 0, nl = 0;
+    int rc = jfsx_parse_header(obj, olen, &kl, &nl);
+    if (rc) return rc;
+    const uint8_t *o = (const uint8_t *)obj;
+    if (expect_crc && !got_crc) return JFSX_EINVAL;
+    if (nl != 12) return JFSX_ETAG;
+    const uint64_t hdr = 3 + (uint64_t)kl + nl;
+    if (olen - hdr < 16) return JFSX_ETAG;
+    const uint64_t len = olen - hdr - 16;
+    const RangeWin w = range_window(len, off, limit);
+    if (out_cap < w.n || (w.n && !out)) return JFSX_EINVAL;
+    jfsx_rblk b;
+    memset(&b, 0, sizeof(b));
+    memcpy(b.key, key, 32);
+    memcpy(b.nonce, o + 3 + kl, 12);
+    memcpy(b.tag, o + hdr + len, 16);
+    b.src = o + hdr;
+    b.len = len;
+    b.off = off;
+    b.limit = limit;
+    b.dst = out;
+    b.dst_cap = out_cap;
+    std::vector<uint8_t> segs;
+    int mode = JFSX_CRC_NONE;
+    if (expect_crc) {
+        segs.resize(4 * nseg_of(len));
+        b.crc = segs.data();
+        mode = JFSX_CRC_GEN | JFSX_CRC_CT;
+    }
+    if ((rc = open(&b, mode))) return rc;
+    if (expect_crc) {
+        if ((rc = jfsx_object_crc32c(o, hdr, segs.data(), len, o + hdr + len, got_crc))) return rc;
+        if (*got_crc != *expect_crc) {
+            if (w.n) memset(out, 0, w.n);
+            return JFSX_ECRC;
+        }
+    }
+    if (b.status == JFSX_ETAG) return JFSX_ETAG;
+    if (out_len) *out_len = w.n;
+    return 0;
+}
+}  // namespace
+
+extern "C" int jfsx_data_decrypt_range(jfsx_ctx *c, int algo, const uint8_t key[32], const void *obj, uint64_t olen,
+                                       uint64_t off, int64_t limit, void *out, uint64_t out_cap, uint64_t *out_len,
+                                       const uint32_t *expect_crc, uint32_t *got_crc) {
+    if (!c || (algo != JFSX_AES256GCM && algo != JFSX_CHACHA20P1305)) return JFSX_EINVAL;
+    return data_decrypt_range([&](jfsx_rblk *b, int m) { return jfsx_open_range_batch(c, algo, 1, b, m, JFSX_MEM_HOST); },
+                              key, obj, olen, off, limit, out, out_cap, out_len, expect_crc, got_crc);
+}
+
+// Host-only view of plan_range (no device, no context), for tests; not part of
+// the ABI (undeclared in jfsx.h).  kind 0 GCM, 1 ChaCha20-Poly1305.  blocks
+// (nullable): n x 8 words o, n, w0, w1, slot0, nslots, main tasks, auth tasks;
+// sizes (nullable): the main planner's task bytes, the auth planner's, the
+// main and auth slots per task; tasks (nullable): up to cap x 5 words blk,
+// kernel (0 main, 1 auth), c0, c1, slot0 in plan order, *ntasks their number.
+extern "C" int jfsx_debug_range_plan(int kind, int n, const uint64_t *lens, const uint64_t *offs, const int64_t *limits,
+                                     uint64_t *blocks, uint64_t *sizes, uint64_t *tasks, uint64_t cap,
+                                     uint64_t *ntasks) {
+    if (kind < kPlanGcm || kind > kPlanCp || n < 0 || (n && (!lens || !offs || !limits))) return JFSX_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (lens[i] > (kind == kPlanGcm ? kGcmMaxLen : kCpMaxLen) || limits[i] < -1) return JFSX_EINVAL;
+    const bool gcm = kind == kPlanGcm;
+    const RangePlan p = plan_range(gcm, n, lens, offs, limits);
+    for (int i = 0; blocks && i < n; i++) {
+        const uint64_t v[8] = {p.win[i].o, p.win[i].n, p.win[i].w0, p.win[i].w1,
+                               p.slot0[i], p.nslots[i], p.n_main[i], p.n_auth[i]};
+        memcpy(blocks + 8 * i, v, sizeof(v));
+    }
+    if (sizes) {
+        sizes[0] = p.main_bytes;
+        sizes[1] = p.auth_bytes;
+        sizes[2] = gcm ? kSlotsPerTask : kCpWaves;
+        sizes[3] = gcm ? kGcmAuthWaves : kCpAuthWaves;
+    }
+    if (ntasks) *ntasks = p.main.size() + p.auth.size();
+    if (tasks && cap) {
+        // plan order: block by block, a block's main tasks, then its auth tasks
+        size_t k = 0, mi = 0, ai = 0;
+        for (int i = 0; i < n && k < cap; i++) {
+            for (; mi < p.main.size() && p.main[mi].blk == (uint32_t)i; mi++) {
+                if (k >= cap) break;
+                const uint64_t v[5] = {(uint64_t)i, 0, p.main[mi].c0, p.main[mi].c1, p.main[mi].slot0};
+                memcpy(tasks + 5 * k++, v, sizeof(v));
+            }
+            for (; ai < p.auth.size() && p.auth[ai].blk == (uint32_t)i; ai++) {
+                if (k >= cap) break;
+                const uint64_t v[5] = {(uint64_t)i, 1, p.auth[ai].c0, p.auth[ai].c1, p.auth[ai].slot0};
+                memcpy(tasks + 5 * k++, v, sizeof(v));
+            }
+        }
+    }
+    return 0;
+}
+
+// The aggregator's ranged Open: one more op, defined here because its batch
+// call is (jfsx_agg.cpp's agg_submit_ext).  The engine stages a host request's
+// pageable memory itself (run_open_range), so the caller's record goes in as
+// it is.
+namespace jfsx {
+typedef int (*AggBatchFn)(jfsx_ctx *c, int algo, int n, void *items, int mode, int mem);
+int agg_submit_ext(jfsx_agg *a, AggBatchFn fn, int algo, int mode, int mem, void *item, size_t item_size,
+                   uint64_t bytes);
+}  // namespace jfsx
+
+extern "C" int jfsx_agg_open_range(jfsx_agg *a, int algo, jfsx_rblk *blk, int crc_mode, int mem) {
+    if (!a || !blk || (algo != JFSX_AES256GCM && algo != JFSX_CHACHA20P1305)) return JFSX_EINVAL;
+    return jfsx::agg_submit_ext(
+        a,
+        [](jfsx_ctx *c, int al, int n, void *items, int mode, int m) {
+            return jfsx_open_range_batch(c, al, n, (jfsx_rblk *)items, mode, m);
+        },
+        algo, crc_mode, mem, blk, sizeof(jfsx_rblk), blk->len);
 }

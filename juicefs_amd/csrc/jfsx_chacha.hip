@@ -364,6 +364,92 @@ __global__ __launch_bounds__(kCpWaves * 64) void cp_main_k(const Task *__restric
 }
 
 // ---------------------------------------------------------------------------
+// cp_auth: Poly1305 of a task's rows without the cipher (ranged Open, the
+// segments outside the window).  cp_task's Poly1305 stream and nothing else:
+// one workgroup per task, kCpAuthWaves waves, each a contiguous run of the
+// task's 4 KiB rows, a lane's 64 bytes per row as four Horner steps (r between
+// them, r^253 across rows), then cp_task's lift and slot write, so
+// cp_finalize_k lifts these slots like any others.  No LDS, and a quarter of
+// cp_main_k's VALU work per row: the next row's loads are issued ahead of the
+// row's arithmetic, and the CU holds eight workgroups.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kCpAuthWaves * 64) void cp_auth_k(const Task *__restrict__ tasks,
+                                                               const BlkDev *__restrict__ blks,
+                                                               const CpSched *__restrict__ sched,
+                                                               uint32_t *__restrict__ partial,
+                                                               uint32_t *__restrict__ pexp) {
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const Task task = tasks[blockIdx.x];
+    const BlkDev blk = blks[task.blk];
+    const CpSched *sch = sched + task.blk;
+    const P5 r1 = p_load(sch->r), r253 = p_load(sch->r253);
+    uint32_t s1[5], s253[5];
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+        s1[i] = 5u * r1.l[i];
+        s253[i] = 5u * r253.l[i];
+    }
+    const uint64_t c0 = task.c0, c1 = task.c1;
+    const uint64_t nrows = (c1 - c0 + 4095) / 4096;
+    const uint64_t ra = wave * nrows / kCpAuthWaves, rb = (wave + 1) * nrows / kCpAuthWaves;
+    const uint64_t sub0 = c0 + ra * 4096;
+    const uint64_t sub1 = rb > ra ? (c0 + rb * 4096 < c1 ? c0 + rb * 4096 : c1) : sub0;
+    const uint64_t rf = (sub1 - sub0) / 4096;  // full rows; every load of the loop lies in [sub0, sub0 + 4096 rf)
+    const uint8_t *p = blk.src + sub0 + 64 * lane;
+    P5 A = p_zero();
+    uint64_t jlast = 0;
+    bool has = false;
+    uint4 nx[4];
+    if (rf) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) nx[q] = gld16(p + 16 * q);
+    }
+    for (uint64_t r = 0; r < rf; r++) {
+        uint4 d[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) d[q] = nx[q];
+        if (r + 1 < rf) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) nx[q] = gld16(p + 4096 * (r + 1) + 16 * q);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+            A = q == 0 ? p_mul_add(A, r253, s253, p_from_words(d[q].x, d[q].y, d[q].z, d[q].w, 1))
+                       : p_mul_add(A, r1, s1, p_from_words(d[q].x, d[q].y, d[q].z, d[q].w, 1));
+    }
+    if (rf) {
+        has = true;
+        jlast = (sub0 + 4096 * (rf - 1) + 64 * lane + 48) >> 4;
+    }
+    // the run's ragged last row (the block's tail): pieces past the end are
+    // skipped, a partial piece is zero padded (load_piece)
+    const uint64_t row = sub0 + 4096 * rf;
+    if (row < sub1) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const uint64_t o = row + 64 * lane + 16 * q;
+            if (o >= sub1) break;
+            const uint4 c = load_piece(blk.src, o, sub1);
+            A = p_add(p_mul(A, q == 0 ? r253 : r1), p_from_words(c.x, c.y, c.z, c.w, 1));
+            jlast = o >> 4;
+            has = true;
+        }
+    }
+    // cp_task's stream epilogue
+    const uint64_t wend = (sub1 + 15) >> 4;
+    P5 z = p_zero();
+    if (has && sub1 > sub0) z = p_freeze(p_mul(A, p_pow(sch->r2k, wend + 1 - jlast)));
+    z = p_wave_sum(z);
+    if (lane == 0) {
+        const uint32_t slot = task.slot0 + wave;
+#pragma unroll
+        for (int i = 0; i < 5; i++) partial[8 * slot + i] = z.l[i];
+        const uint64_t nblk = (blk.len + 15) >> 4;
+        pexp[slot] = (uint32_t)(nblk - wend);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // keysetup: one wave per block
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void cp_keysetup_k(const KeyIn *__restrict__ keys, const BlkDev *__restrict__ blks,
@@ -468,6 +554,12 @@ void launch_cp_main(hipStream_t s, int ntasks, int ncu, uint32_t *queue, bool op
         case 6: L(false, 6); break;
     }
 #undef L
+}
+
+void launch_cp_auth(hipStream_t s, int ntasks, const Task *tasks, const BlkDev *blks, const CpSched *sched,
+                    uint32_t *partial, uint32_t *pexp) {
+    if (ntasks > 0)
+        hipLaunchKernelGGL(cp_auth_k, dim3(ntasks), dim3(kCpAuthWaves * 64), 0, s, tasks, blks, sched, partial, pexp);
 }
 
 void launch_cp_finalize(hipStream_t s, int n, bool open, int crc_mode, const BlkDev *blks, const CpSched *sched,

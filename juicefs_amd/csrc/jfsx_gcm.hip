@@ -1234,6 +1234,126 @@ __global__ __launch_bounds__(GcmShape<BS>::threads) void gcm_main_k(const Task *
 }
 
 // ---------------------------------------------------------------------------
+// gcm_auth: GHASH of a task's rows without the cipher (ranged Open, the
+// segments outside the window).  One workgroup per task, kAuthWaves waves, each
+// wave a contiguous run of the task's 1 KiB rows: load, ghash_step, and at the
+// wave's end the lift and the slot write of gcm_task, so gcm_finalize_k lifts
+// these slots like any others.  The LDS holds the task's GHASH table alone, at
+// gcm_main's offset kLdsGh so that ghash_step is the same code, with the basis
+// staged below it: 88 KiB, one workgroup of 16 waves per CU (4 per SIMD).  The
+// kernel has no AES table to stage, so it is not persistent: a workgroup's
+// only set-up is the table of its task's key.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kAuthLdsBytes = kLdsGh + 65536;
+constexpr int kAuthPf = 4;  // rows of loads a wave keeps in flight
+
+__global__ __launch_bounds__(kGcmAuthWaves * 64) void gcm_auth_k(const Task *__restrict__ tasks,
+                                                                 const BlkDev *__restrict__ blks,
+                                                                 const GcmSched *__restrict__ sched,
+                                                                 uint32_t *__restrict__ partial,
+                                                                 uint32_t *__restrict__ pexp) {
+    __shared__ __attribute__((aligned(16))) char lds[kAuthLdsBytes];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const Task task = tasks[blockIdx.x];
+    const BlkDev blk = blks[task.blk];
+    const GcmSched *sch = sched + task.blk;
+    if (tid < 128) reinterpret_cast<uint4 *>(lds)[tid] = reinterpret_cast<const uint4 *>(sch->basis)[tid];
+    __syncthreads();
+    {
+        // as gcm_task builds it: entry (b, j) is the XOR of basis[8j + k] over the set bits 7 - k of b
+        uint4 *lg = reinterpret_cast<uint4 *>(lds + kLdsGh);
+        const uint4 *lb = reinterpret_cast<const uint4 *>(lds);
+        for (uint32_t u = tid; u < 1024; u += kGcmAuthWaves * 64) {
+            const uint32_t j = u & 15, blow = u >> 4;
+            uint4 z = make_uint4(0, 0, 0, 0);
+#pragma unroll
+            for (int k = 2; k < 8; k++) {
+                if ((blow >> (7 - k)) & 1) {
+                    const uint4 v = lb[8 * j + k];
+                    z.x ^= v.x; z.y ^= v.y; z.z ^= v.z; z.w ^= v.w;
+                }
+            }
+            const uint4 h0 = lb[8 * j], h1 = lb[8 * j + 1];
+            lg[(blow << 4) | j] = z;
+            lg[((blow | 64) << 4) | j] = make_uint4(z.x ^ h1.x, z.y ^ h1.y, z.z ^ h1.z, z.w ^ h1.w);
+            lg[((blow | 128) << 4) | j] = make_uint4(z.x ^ h0.x, z.y ^ h0.y, z.z ^ h0.z, z.w ^ h0.w);
+            lg[((blow | 192) << 4) | j] =
+                make_uint4(z.x ^ h0.x ^ h1.x, z.y ^ h0.y ^ h1.y, z.z ^ h0.z ^ h1.z, z.w ^ h0.w ^ h1.w);
+        }
+    }
+    __syncthreads();
+
+    const GhLane gl = gh_lane(lane);
+    const uint64_t c0 = task.c0, c1 = task.c1;
+    const uint64_t nrows = (c1 - c0 + 1023) / 1024;
+    const uint64_t ra = wave * nrows / kGcmAuthWaves, rb = (wave + 1) * nrows / kGcmAuthWaves;
+    const uint64_t sub0 = c0 + ra * 1024;
+    const uint64_t sub1 = rb > ra ? (c0 + rb * 1024 < c1 ? c0 + rb * 1024 : c1) : sub0;
+    const uint64_t rf = (sub1 - sub0) / 1024;  // full rows; every load below lies in [sub0, sub0 + 1024 rf)
+    const uint8_t *p = blk.src + sub0 + 16 * lane;
+    uint32_t acc[4] = {0, 0, 0, 0};
+    uint64_t jlast = 0;
+    bool has = false;
+    uint4 pf[kAuthPf];
+#pragma unroll
+    for (int q = 0; q < kAuthPf; q++)
+        if ((uint64_t)q < rf) pf[q] = gld16_nt(p + 1024 * q);
+    uint64_t r = 0;
+    for (; r + kAuthPf <= rf; r += kAuthPf) {
+#pragma unroll
+        for (int q = 0; q < kAuthPf; q++) {
+            const uint4 c = pf[q];
+            if (r + kAuthPf + q < rf) pf[q] = gld16_nt(p + 1024 * (r + kAuthPf + q));
+            ghash_step(lds, acc, gl, c);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < kAuthPf; q++)
+        if (r + q < rf) ghash_step(lds, acc, gl, pf[q]);
+    if (rf) {
+        has = true;
+        jlast = (sub0 + 1024 * (rf - 1) + 16 * lane) >> 4;
+    }
+    // the run's ragged last row (the block's tail): lanes past the end keep their sum
+    const uint64_t row = sub0 + 1024 * rf;
+    if (row < sub1) {
+        const uint64_t o = row + 16 * lane;
+        const bool valid = o < sub1;
+        uint4 c = make_uint4(0, 0, 0, 0);
+        if (valid) c = load_piece(blk.src, o, sub1);  // zero filled past the end
+        uint32_t t[4] = {acc[0], acc[1], acc[2], acc[3]};
+        ghash_step(lds, t, gl, c);
+        if (valid) {
+            acc[0] = t[0]; acc[1] = t[1]; acc[2] = t[2]; acc[3] = t[3];
+            jlast = o >> 4;
+            has = true;
+        }
+    }
+    // the wave-end lift and the slot write of gcm_task
+    const uint64_t nblk = (blk.len + 15) >> 4;
+    const uint64_t wend = (sub1 + 15) >> 4;
+    g128 z = {{0, 0, 0, 0}};
+    if (has && sub1 > sub0) {
+        const uint32_t e = (uint32_t)(wend + 1 - jlast);  // in [2, 65]
+        uint32_t a[4];
+        gh_rho_inv(acc, gl, a);
+        z = g_mul_ct_call(g_from_mem(a), g_from_mem(sch->hpow[e]));
+    }
+    uint32_t zm[4];
+    g_to_mem(z, zm);
+    for (int k = 0; k < 4; k++) zm[k] = wave_xor(zm[k]);
+    if (lane == 0) {
+        const uint32_t slot = task.slot0 + wave;
+        partial[4 * slot + 0] = zm[0];
+        partial[4 * slot + 1] = zm[1];
+        partial[4 * slot + 2] = zm[2];
+        partial[4 * slot + 3] = zm[3];
+        pexp[slot] = (uint32_t)(nblk - wend);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // keysetup: one wave per block; AES via the (global) T-table image
 // ---------------------------------------------------------------------------
 // keysetup's lookups go to a compact copy of T0 | T2 staged in LDS (entry x
@@ -1623,6 +1743,12 @@ void launch_gcm_main(hipStream_t s, int ntasks, int ncu, uint32_t *queue, bool o
         case 6: L(false, 6); break;
     }
 #undef L
+}
+
+void launch_gcm_auth(hipStream_t s, int ntasks, const Task *tasks, const BlkDev *blks, const GcmSched *sched,
+                     uint32_t *partial, uint32_t *pexp) {
+    if (ntasks > 0)
+        hipLaunchKernelGGL(gcm_auth_k, dim3(ntasks), dim3(kGcmAuthWaves * 64), 0, s, tasks, blks, sched, partial, pexp);
 }
 
 void launch_gcm_finalize(hipStream_t s, int n, bool open, int crc_mode, const BlkDev *blks, const GcmSched *sched,

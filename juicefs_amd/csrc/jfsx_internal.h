@@ -271,6 +271,16 @@ void launch_cp_main(hipStream_t s, int ntasks, int ncu, uint32_t *queue, bool op
                     const BlkDev *blks, const CpSched *sched, uint32_t *partial, uint32_t *pexp, DevTables t);
 void launch_cp_finalize(hipStream_t s, int n, bool open, int crc_mode, const BlkDev *blks, const CpSched *sched,
                         const uint32_t *partial, const uint32_t *pexp, BlkOut *out);
+// Ranged Open (jfsx_open_range_batch): the segments of a block outside the
+// window are authenticated without the cipher.  One workgroup per task (plan
+// order, no queue), one partial slot per wave in the format the finalize
+// kernels lift; tasks are whole segments but for a block's tail.
+constexpr int kGcmAuthWaves = 16;  // gcm_auth_k: 88 KiB of LDS, one workgroup per CU
+constexpr int kCpAuthWaves = 4;    // cp_auth_k: no LDS, eight workgroups per CU
+void launch_gcm_auth(hipStream_t s, int ntasks, const Task *tasks, const BlkDev *blks, const GcmSched *sched,
+                     uint32_t *partial, uint32_t *pexp);
+void launch_cp_auth(hipStream_t s, int ntasks, const Task *tasks, const BlkDev *blks, const CpSched *sched,
+                    uint32_t *partial, uint32_t *pexp);
 void launch_crc_segments(hipStream_t s, int ntasks, const Task *tasks, const BlkDev *blks, DevTables t);
 void launch_crc_finalize(hipStream_t s, int n, int crc_mode, const BlkDev *blks, BlkOut *out);
 // Hadoop file checksum (jfsx_crc.hip): CRC32C per 512-byte chunk of the tasks'

@@ -413,6 +413,19 @@ class DataEncryptor:
         raise.  checksums (optional, one decimal string or None per object) are
         the object-store CRC32Cs to verify in the same pass; a mismatch yields
         the store's "verify checksum failed" error (checksum.go:65)."""
+        return self._decrypt_batch(ciphertexts, checksums, None)
+
+    def DecryptRangeBatch(self, ciphertexts, windows, checksums=None):
+        """DecryptBatch with encrypted.Get's window: windows[i] = (off, limit)
+        of object i, and the result is plaintext[o:o + n] by Go's slice rule
+        (encrypt.go:246-253).  The whole object is authenticated (and
+        checksummed, with checksums); only the window is decrypted and
+        returned (jfsx_open_range_batch).  Same errors as DecryptBatch."""
+        if len(windows) != len(ciphertexts):
+            raise ValueError("one (off, limit) per object")
+        return self._decrypt_batch(ciphertexts, checksums, windows)
+
+    def _decrypt_batch(self, ciphertexts, checksums, windows):
         import numpy as np
         from .checksum import ChecksumVerifyError, parse_checksum
         res = [None] * len(ciphertexts)
@@ -457,23 +470,38 @@ class DataEncryptor:
                 continue
             n = len(ct) - 16
             src = np.frombuffer(ct[:n], np.uint8).copy() if n else np.zeros(1, np.uint8)
-            dst = np.zeros(max(n, 1), np.uint8)
+            if windows is not None:
+                off, limit = windows[i]
+                wn = E.range_window(n, off, limit)[1]
+                dst = np.zeros(max(wn, 1), np.uint8)
+                spec = {"key": key, "nonce": nonce, "src": src.ctypes.data if n else None, "dst": dst.ctypes.data,
+                        "dst_cap": wn, "len": n, "off": off, "limit": limit, "tag": ct[n:]}
+            else:
+                dst = np.zeros(max(n, 1), np.uint8)
+                spec = {"key": key, "nonce": nonce, "src": src.ctypes.data if n else None, "dst": dst.ctypes.data,
+                        "len": n, "tag": ct[n:]}
             bufs.append((src, dst, n))
             idx.append(i)
-            spec = {"key": key, "nonce": nonce, "src": src.ctypes.data if n else None, "dst": dst.ctypes.data,
-                    "len": n, "tag": ct[n:]}
             if checksums is not None:
                 sb = np.zeros(4 * max(1, -(-n // (32 << 10))), np.uint8)
                 segs.append((sb, c[:3 + keyLen + nonceLen], checksums[i]))
                 spec["crc"] = sb.ctypes.data
             specs.append(spec)
         if specs:
-            arr, cnt = self.eng.make_blocks(specs)
             mode = E.CRC_GEN | E.CRC_CT if checksums is not None else E.CRC_NONE
-            if self._agg is not None and cnt == 1:
-                self._agg.open(self.algo, arr[0], mode, E.MEM_HOST)
+            if windows is not None:
+                arr, cnt = self.eng.make_rblocks(specs)
+                if self._agg is not None and cnt == 1:
+                    self._agg.open_range(self.algo, arr[0], mode, E.MEM_HOST)
+                else:
+                    self.eng.open_range_batch(self.algo, arr, cnt, mode, E.MEM_HOST)
+                self.range_calls = getattr(self, "range_calls", 0) + 1
             else:
-                self.eng.open_batch(self.algo, arr, cnt, mode, E.MEM_HOST)
+                arr, cnt = self.eng.make_blocks(specs)
+                if self._agg is not None and cnt == 1:
+                    self._agg.open(self.algo, arr[0], mode, E.MEM_HOST)
+                else:
+                    self.eng.open_batch(self.algo, arr, cnt, mode, E.MEM_HOST)
             for k, i in enumerate(idx):
                 if want[i] is not None:
                     sb, hdr, _ = segs[k]
@@ -483,6 +511,8 @@ class DataEncryptor:
                         continue
                 if arr[k].status == E.ETAG:
                     res[i] = EncryptError(_ERR_OPEN[self.algo])
+                elif windows is not None:
+                    res[i] = bufs[k][1][:arr[k].out_len].tobytes()
                 else:
                     res[i] = bufs[k][1][:bufs[k][2]].tobytes()
         # objects that failed before the AEAD pass (header, key unwrap, nonce):
@@ -538,9 +568,22 @@ class MemStorage:
         return sorted(k for k in self._d if k.startswith(prefix))
 
 
+def _plain_len(ciphertext):
+    """plaintext bytes the object's header implies, None where Decrypt would
+    reject the object before the AEAD (encrypt.go:197-201)"""
+    c = ciphertext
+    if len(c) < 3 or 3 + (c[0] << 8) + c[1] + c[2] >= len(c):
+        return None
+    return max(0, len(c) - 3 - ((c[0] << 8) + c[1]) - c[2] - 16)
+
+
 class Encrypted:
-    """encrypted ObjectStorage: Put seals the whole object, Get opens the whole
-    object then slices [off, off+limit) (encrypt.go:232-267)."""
+    """encrypted ObjectStorage: Put seals the whole object; Get fetches the
+    whole object and returns [off, off+limit) of its plaintext
+    (encrypt.go:232-267).  A read of at most a quarter of the object, the only
+    ranged Get the reference issues (cached_store.go:152), authenticates the
+    whole object but decrypts and brings back the window alone
+    (DecryptRangeBatch); every other read opens the whole object and slices."""
 
     def __init__(self, store, enc):
         self.store = store
@@ -555,18 +598,31 @@ class Encrypted:
         return getattr(self.store, "GetChecksum", None) is not None and not self.store.disableChecksum \
             and hasattr(self.enc, "EncryptBatch")
 
+    def _ranged(self, ciphertext, off, limit):
+        n = _plain_len(ciphertext)
+        return n is not None and limit >= 0 and 4 * limit <= n and off >= 0 and off < 1 << 64 \
+            and hasattr(self.enc, "DecryptRangeBatch")
+
     def Get(self, key, off=0, limit=-1):
-        if self._fused() and self.store.GetChecksum(key) is not None:
-            ciphertext = self.store.inner.Get(key, 0, -1)
+        from .checksum import ChecksumVerifyError
+        fused = self._fused() and self.store.GetChecksum(key) is not None
+        ciphertext = self.store.inner.Get(key, 0, -1) if fused else self.store.Get(key, 0, -1)
+        if self._ranged(ciphertext, off, limit):
+            r = self.enc.DecryptRangeBatch([ciphertext], [(off, limit)],
+                                           [self.store.GetChecksum(key)] if fused else None)[0]
+            if fused and isinstance(r, ChecksumVerifyError):
+                raise r  # a read error of the store (io.ReadAll), not wrapped
+            if isinstance(r, Exception):
+                raise EncryptError("Decrypt: %s" % r)
+            return r
+        if fused:
             r = self.enc.DecryptBatch([ciphertext], [self.store.GetChecksum(key)])[0]
-            from .checksum import ChecksumVerifyError
             if isinstance(r, ChecksumVerifyError):
                 raise r  # a read error of the store (io.ReadAll), not wrapped
             if isinstance(r, Exception):
                 raise EncryptError("Decrypt: %s" % r)
             plain = r
         else:
-            ciphertext = self.store.Get(key, 0, -1)
             try:
                 plain = self.enc.Decrypt(ciphertext)
             except Exception as e:

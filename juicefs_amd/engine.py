@@ -61,6 +61,7 @@ EXPORTS = [
     "jfsx_file_checksum_span", "jfsx_file_checksum_batch", "jfsx_file_checksum_fold",
     "jfsx_load_batch", "jfsx_store_batch", "jfsx_load_objects", "jfsx_object_bound", "jfsx_object_bound_key", "jfsx_store_objects",
     "jfsx_compact_plan", "jfsx_gather_batch", "jfsx_compact_objects",
+    "jfsx_open_range_batch", "jfsx_agg_open_range", "jfsx_data_decrypt_range",
 ]
 
 
@@ -97,6 +98,17 @@ class jfsx_blk(ctypes.Structure):
         ("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("len", ctypes.c_uint64),
         ("tag", ctypes.c_uint8 * 16), ("crc", ctypes.c_void_p), ("status", ctypes.c_int32),
         ("crc_bad_seg", ctypes.c_int32), ("crc_got", ctypes.c_uint32), ("crc_expect", ctypes.c_uint32),
+    ]
+
+
+class jfsx_rblk(ctypes.Structure):
+    """One block of jfsx_open_range_batch: encrypted.Get(key, off, limit)."""
+    _fields_ = [
+        ("key", ctypes.c_uint8 * 32), ("nonce", ctypes.c_uint8 * 12), ("reserved", ctypes.c_uint32),
+        ("tag", ctypes.c_uint8 * 16), ("src", ctypes.c_void_p), ("len", ctypes.c_uint64),
+        ("off", ctypes.c_uint64), ("limit", ctypes.c_int64), ("dst", ctypes.c_void_p),
+        ("dst_cap", ctypes.c_uint64), ("crc", ctypes.c_void_p), ("out_len", ctypes.c_uint64),
+        ("status", ctypes.c_int32), ("reserved2", ctypes.c_int32),
     ]
 
 
@@ -317,6 +329,9 @@ def load_library(path=LIB_PATH):
                                       ctypes.POINTER(I), I, ctypes.POINTER(jfsx_piece), ctypes.POINTER(I)]),
             "jfsx_gather_batch": (I, [P, I, ctypes.POINTER(jfsx_gsrc), I, ctypes.POINTER(jfsx_gdst), I,
                                       ctypes.POINTER(jfsx_piece), I]),
+            "jfsx_open_range_batch": (I, [P, I, I, ctypes.POINTER(jfsx_rblk), I, I]),
+            "jfsx_agg_open_range": (I, [P, I, ctypes.POINTER(jfsx_rblk), I, I]),
+            "jfsx_data_decrypt_range": (I, [P, I, P, P, U64, U64, ctypes.c_int64, P, U64, ctypes.POINTER(U64), P, P]),
             "jfsx_compact_objects": (I, [P, P, U32, I, I, I, ctypes.POINTER(jfsx_oblk), I, I,
                                          ctypes.POINTER(jfsx_soblk), ctypes.POINTER(jfsx_cpage), I, I,
                                          ctypes.POINTER(jfsx_piece)]),
@@ -403,6 +418,52 @@ def debug_plan(kind, lens):
         if rc:
             raise EngineError(rc, "jfsx_debug_plan")
     return tb.value, ns.value, [tuple(int(x) for x in t) for t in tasks]
+
+
+def range_window(length, off, limit):
+    """Go's slice rule of encrypted.Get (encrypt.go:246-253): (o, n)."""
+    o = min(off, length)
+    n = length - o if limit == -1 or limit > length - o else limit
+    return o, n
+
+
+def debug_range_plan(kind, lens, offs, limits):
+    """How jfsx_open_range_batch would cut a batch of blocks of these lengths
+    and (off, limit) windows (host only, no device; jfsx_debug_range_plan is a
+    test hook outside the ABI).  kind: PLAN_GCM or PLAN_CHACHA.  Returns a dict:
+    blocks = per block {o, n, w0, w1, slot0, nslots, n_main, n_auth} (the
+    widened window is [w0, w1)), main_bytes / auth_bytes = the two planners'
+    task sizes, main_slots / auth_slots = partial slots per task, tasks = (blk,
+    kernel, c0, c1, slot0) in plan order with kernel 0 the main kernel and 1
+    the auth kernel."""
+    fn = load_library().jfsx_debug_range_plan
+    U64P = ctypes.POINTER(ctypes.c_uint64)
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, U64P]
+    ln = np.ascontiguousarray(lens, dtype=np.uint64)
+    of = np.ascontiguousarray(offs, dtype=np.uint64)
+    lm = np.ascontiguousarray(limits, dtype=np.int64)
+    assert ln.size == of.size == lm.size
+    n = int(ln.size)
+    blocks = np.zeros((max(n, 1), 8), np.uint64)
+    sizes = np.zeros(4, np.uint64)
+    nt = ctypes.c_uint64()
+    args = (kind, n, ln.ctypes.data if n else None, of.ctypes.data if n else None, lm.ctypes.data if n else None)
+    rc = fn(*args, blocks.ctypes.data, sizes.ctypes.data, None, 0, ctypes.byref(nt))
+    if rc:
+        raise EngineError(rc, "jfsx_debug_range_plan")
+    tasks = np.zeros((max(nt.value, 1), 5), np.uint64)
+    rc = fn(*args, None, None, tasks.ctypes.data, nt.value, None)
+    if rc:
+        raise EngineError(rc, "jfsx_debug_range_plan")
+    names = ("o", "n", "w0", "w1", "slot0", "nslots", "n_main", "n_auth")
+    return {
+        "blocks": [dict(zip(names, (int(x) for x in blocks[i]))) for i in range(n)],
+        "main_bytes": int(sizes[0]), "auth_bytes": int(sizes[1]),
+        "main_slots": int(sizes[2]), "auth_slots": int(sizes[3]),
+        "tasks": [tuple(int(x) for x in tasks[i]) for i in range(nt.value)],
+    }
 
 
 def gen_key(seed, block):
@@ -673,6 +734,33 @@ class Engine:
 
     def open_batch(self, algo, blks, n, crc_mode=CRC_NONE, mem=MEM_DEVICE):
         self._check(self.L.jfsx_open_batch(self.ctx, algo, n, blks, crc_mode, mem), "jfsx_open_batch")
+
+    @staticmethod
+    def make_rblocks(specs):
+        """jfsx_rblk array from dicts: key, nonce, tag, src, len, off, limit
+        (default -1), dst, dst_cap, crc."""
+        specs = list(specs)
+        arr = (jfsx_rblk * max(len(specs), 1))()
+        for i, s in enumerate(specs):
+            b = arr[i]
+            ctypes.memmove(b.key, bytes(s["key"]), 32)
+            ctypes.memmove(b.nonce, bytes(s["nonce"]), 12)
+            ctypes.memmove(b.tag, bytes(s["tag"]), 16)
+            b.src = s.get("src")
+            b.len = s["len"]
+            b.off = s.get("off", 0)
+            b.limit = s.get("limit", -1)
+            b.dst = s.get("dst")
+            b.dst_cap = s.get("dst_cap", 0)
+            b.crc = s.get("crc")
+        return arr, len(specs)
+
+    def open_range_batch(self, algo, rblks, n, crc_mode=CRC_NONE, mem=MEM_DEVICE):
+        """jfsx_open_range_batch: every block's tag checked over all of C, the
+        window [o, o + n) of its plaintext released into dst (out_len, status
+        per block).  crc_mode CRC_NONE or CRC_GEN | CRC_CT."""
+        self._check(self.L.jfsx_open_range_batch(self.ctx, algo, n, rblks, crc_mode, mem), "jfsx_open_range_batch")
+        self.range_calls = getattr(self, "range_calls", 0) + 1
 
     def crc32c_segments(self, ranges, n, mode=CRC_GEN, mem=MEM_DEVICE):
         self._check(self.L.jfsx_crc32c_segments(self.ctx, n, ranges, mode, mem), "jfsx_crc32c_segments")
@@ -1174,6 +1262,25 @@ class Engine:
         pt = out[:olen.value].tobytes() if rc == 0 else b""
         return (rc, pt, segs.tobytes()) if seg_crc else (rc, pt)
 
+    def data_decrypt_range(self, algo, key, obj, off, limit, expect_crc=None):
+        """jfsx_data_decrypt_range: (rc, plaintext[off:off+limit] by Go's slice
+        rule) -- data_decrypt with the window; rc JFSX_ECRC when expect_crc is
+        given and the object checksum differs (.last_got_crc then holds the
+        computed value)."""
+        o = _u8(obj)
+        _, n = range_window(_obj_plain_len(o), off, limit)
+        out = np.empty(max(n, 1), np.uint8)
+        olen = ctypes.c_uint64()
+        exp = ctypes.c_uint32(expect_crc or 0)
+        got = ctypes.c_uint32()
+        rc = self.L.jfsx_data_decrypt_range(self.ctx, algo, bytes(key), o.ctypes.data, o.size, off, limit,
+                                            out.ctypes.data, n, ctypes.byref(olen),
+                                            ctypes.byref(exp) if expect_crc is not None else None,
+                                            ctypes.byref(got) if expect_crc is not None else None)
+        self.last_got_crc = got.value
+        self.range_calls = getattr(self, "range_calls", 0) + 1
+        return rc, (out[:olen.value].tobytes() if rc == 0 else b"")
+
     def rsa_key(self, p, q, dp, dq, qinv, label=b"keys"):
         """Device copy of an RSA-2048 or RSA-4096 private key from its CRT
         components (big-endian, 128 or 256 bytes each) for the batch calls and
@@ -1422,6 +1529,11 @@ class Aggregator:
 
     def open(self, algo, blk, crc_mode=CRC_NONE, mem=MEM_HOST):
         self.eng._check(self.L.jfsx_agg_open(self.h, algo, ctypes.byref(blk), crc_mode, mem), "jfsx_agg_open")
+
+    def open_range(self, algo, rblk, crc_mode=CRC_NONE, mem=MEM_HOST):
+        """rblk: a jfsx_rblk (out_len and status are written into it)."""
+        self.eng._check(self.L.jfsx_agg_open_range(self.h, algo, ctypes.byref(rblk), crc_mode, mem),
+                        "jfsx_agg_open_range")
 
     def crc32c(self, rng, mode=CRC_VERIFY, mem=MEM_HOST):
         self.eng._check(self.L.jfsx_agg_crc32c(self.h, ctypes.byref(rng), mode, mem), "jfsx_agg_crc32c")
