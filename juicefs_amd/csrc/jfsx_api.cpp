@@ -1489,6 +1489,138 @@ void par_copy(std::vector<std::pair<char *, const char *>> &ds, const std::vecto
     for (std::thread &t : ts) t.join();
 }
 
+// Host staging of the one-call paths (load, load_objects, store, store_objects,
+// gather, and the upload of the ranged Open).  A caller's buffer that is
+// page-locked is copied by DMA where it lies; a pageable one goes through one
+// pinned bounce buffer that serves both directions: the stream has finished
+// the uploads out of it before it reaches the downloads into it.  The rule of
+// a direction: when every classified buffer of it is pageable the buffer is
+// filled (or emptied) packed and crosses PCIe in one copy of the packed span;
+// otherwise every non-empty item crosses in a copy of its own, from (to) its
+// place in the bounce buffer or the caller's memory.
+// A path classifies (mark) what it may transfer, takes the buffer (reserve)
+// before its first enqueue, and names the items of a transfer when it
+// enqueues it.  The object outlives the call's last stream wait: the buffer
+// goes back to the pool when it dies.
+struct StageItem {
+    void *host;  // the caller's buffer
+    char *dev;   // its place in device memory
+    size_t off;  // its place in the bounce buffer (packed: dev is the span's start + off)
+    size_t len;
+    size_t idx;  // its index in the direction's classification
+};
+
+struct HostStage {
+    struct Dir {
+        std::vector<char> bounced;  // per index; an index never marked (an empty buffer) counts in neither flag
+        bool all = true, any = false;
+    };
+    Dir in, out;
+
+    HostStage() = default;
+    HostStage(const HostStage &) = delete;
+    HostStage &operator=(const HostStage &) = delete;
+    ~HostStage() {
+        if (pool_) bounce_put(pool_, buf_, cap_);
+    }
+
+    void resize(size_t n_in, size_t n_out) {
+        in.bounced.assign(n_in, 0);
+        out.bounced.assign(n_out, 0);
+    }
+    static void mark(Dir &d, size_t i, const void *p, size_t len) {
+        const bool b = !host_pinned(p, len);
+        d.bounced[i] = b;
+        d.all = d.all && b;
+        d.any = d.any || b;
+    }
+    size_t need(size_t up, size_t down) const { return std::max(in.any ? up : 0, out.any ? down : 0); }
+    // the pool's buffer for the packed spans of both directions
+    int reserve(jfsx_ctx *c, size_t up, size_t down) {
+        const size_t n = need(up, down);
+        if (!n) return 0;
+        if (!(buf_ = bounce_get(c, n, &cap_))) return JFSX_ENOMEM;
+        pool_ = c;
+        return 0;
+    }
+    // a buffer of the caller's, of need() bytes, instead: it stays the caller's and no bounce bytes are counted
+    void lend(char *buf) { buf_ = buf; }
+
+    int upload(hipStream_t s, char *dev, size_t span, const std::vector<StageItem> &items) {
+        copy(items, in, true);
+        if (in.all && span) {
+            HIP_OK(hipMemcpyAsync(dev, buf_, span, hipMemcpyHostToDevice, s));
+            return 0;
+        }
+        for (const StageItem &it : items)
+            if (it.len)
+                HIP_OK(hipMemcpyAsync(it.dev, in.bounced[it.idx] ? buf_ + it.off : (const char *)it.host, it.len,
+                                      hipMemcpyHostToDevice, s));
+        return 0;
+    }
+    // span 0: the items do not lie packed in device memory, every one is copied by itself
+    int download(hipStream_t s, const char *dev, size_t span, std::vector<StageItem> items) {
+        down_ = std::move(items);
+        if (out.all && span) {
+            HIP_OK(hipMemcpyAsync(buf_, dev, span, hipMemcpyDeviceToHost, s));
+            return 0;
+        }
+        for (const StageItem &it : down_)
+            if (it.len)
+                HIP_OK(hipMemcpyAsync(out.bounced[it.idx] ? buf_ + it.off : (char *)it.host, it.dev, it.len,
+                                      hipMemcpyDeviceToHost, s));
+        return 0;
+    }
+    // after the wait of a call that succeeded: the bounced items of download() to the caller
+    void copy_out() { copy(down_, out, false); }
+
+  private:
+    void copy(const std::vector<StageItem> &items, const Dir &d, bool up) {
+        std::vector<std::pair<char *, const char *>> cp;
+        std::vector<size_t> cl;
+        for (const StageItem &it : items) {
+            if (!it.len || !d.bounced[it.idx]) continue;
+            if (up) cp.push_back({buf_ + it.off, (const char *)it.host});
+            else cp.push_back({(char *)it.host, buf_ + it.off});
+            cl.push_back(it.len);
+            if (pool_) (up ? pool_->bounce.bytes_in : pool_->bounce.bytes_out) += it.len;
+        }
+        par_copy(cp, cl);
+    }
+    char *buf_ = nullptr;
+    size_t cap_ = 0;
+    jfsx_ctx *pool_ = nullptr;  // the context whose pool buf_ goes back to
+    std::vector<StageItem> down_;
+};
+
+// The wait that ends a phase of a call, whatever its enqueue returned, so that
+// a failure leaves nothing in flight: a stream error becomes JFSX_EIO unless
+// an earlier error stands.
+int wait_stream(jfsx_ctx *c, int rc, const char *what) {
+    const hipError_t se = hipStreamSynchronize(c->stream);
+    if (!rc && se != hipSuccess) {
+        note_hip_error(se, __FILE__, __LINE__, what);
+        rc = JFSX_EIO;
+    }
+    return rc;
+}
+
+void add_elapsed_ms(jfsx_ctx *c, hipEvent_t ev0, hipEvent_t ev1) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) add_kernel_ms(c, ms);
+    else (void)hipGetLastError();
+}
+
+// After a call's last wait: the main-kernel time of a stage that was timed
+// (ok: the call succeeded), and its workspace free for the next call.
+void settle_stage(jfsx_ctx *c, Workspace &w, hipEvent_t ev0, hipEvent_t ev1, bool ok) {
+    if (ok && w.timed && w.nt) add_elapsed_ms(c, ev0, ev1);
+    w.n = 0;
+    w.nt = 0;
+    w.timed = false;
+    w.crc_back = false;
+}
+
 // Host-memory call (host ingest, the per-object shim, checksum() / ReadAt
 // verify on host memory).  The call is cut into groups; for each group the
 // calling thread (1) copies its pageable blocks into a bounce buffer, (2)
@@ -1948,10 +2080,8 @@ int check_load_args(int algo, int codec, int n, const jfsx_lblk *blks, int crc_m
 }
 
 struct LoadState {
-    char *bounce = nullptr;  // pinned staging of the call's pageable images (up) and pages (down)
-    size_t bcap = 0;
-    std::vector<size_t> poff;   // host: page i at load_stage + img_bytes + poff[i], and at bounce + poff[i]
-    std::vector<char> out_b;    // host: page i comes back through the bounce buffer
+    HostStage hs;               // host: the images up, the pages down
+    std::vector<size_t> poff;   // host: page i at load_stage + img_bytes + poff[i]
     size_t h_res = 0;           // offset of the downloaded results in load_h
     size_t crc_off = 0;         // host CRC_GEN: offset of the CRC words behind the results
     int zd_waves = 0;           // zstd: waves of the block-parallel decoder (0: the serial kernel)
@@ -1967,7 +2097,6 @@ int load_enqueue(jfsx_ctx *c, int algo, int codec, int n, const jfsx_lblk *blks,
     // staging: the images, then (host) the pages
     std::vector<size_t> ioff(n);
     st.poff.assign(n, 0);
-    st.out_b.assign(n, 0);
     size_t img_bytes = 0, page_bytes = 0;
     uint64_t crc_words = 0, max_len = 0;
     for (int i = 0; i < n; i++) {
@@ -2004,38 +2133,18 @@ int load_enqueue(jfsx_ctx *c, int algo, int codec, int n, const jfsx_lblk *blks,
     const size_t stage_need = host ? img_bytes + page_bytes : aead ? img_bytes : 0;
     if (stage_need && (rc = ensure_dev(c, &c->load_stage, &c->load_scap, stage_need))) return rc;
     char *d = c->load_d, *h = c->load_h, *stage = c->load_stage;
-    // host: which images and pages go through the bounce pool (pageable caller
-    // memory; page-locked memory is copied by DMA directly).  One buffer serves
-    // both directions: the stream has finished the uploads out of it before it
-    // reaches the downloads into it.
-    std::vector<char> in_b(n, 0);
-    bool all_in = host, all_out = host, any_in = false, any_out = false;
+    // host: the images up and the pages down; an empty one is not classified
+    std::vector<StageItem> up_items, down_items;
     if (host) {
+        st.hs.resize(n, n);
         for (int i = 0; i < n; i++) {
-            if (blks[i].src_len) {
-                in_b[i] = !host_pinned(blks[i].src, blks[i].src_len);
-                all_in = all_in && in_b[i];
-                any_in = any_in || in_b[i];
-            }
-            if (blks[i].len) {
-                st.out_b[i] = !host_pinned(blks[i].dst, blks[i].len);
-                all_out = all_out && st.out_b[i];
-                any_out = any_out || st.out_b[i];
-            }
+            const jfsx_lblk &b = blks[i];
+            if (b.src_len) HostStage::mark(st.hs.in, i, b.src, b.src_len);
+            if (b.len) HostStage::mark(st.hs.out, i, b.dst, b.len);
+            up_items.push_back({(void *)b.src, stage + ioff[i], ioff[i], b.src_len, (size_t)i});
+            down_items.push_back({b.dst, stage + img_bytes + st.poff[i], st.poff[i], b.len, (size_t)i});
         }
-        const size_t need = std::max(any_in ? img_bytes : 0, any_out ? page_bytes : 0);
-        if (need) {
-            if (!(st.bounce = bounce_get(c, need, &st.bcap))) return JFSX_ENOMEM;
-            std::vector<std::pair<char *, const char *>> cp;
-            std::vector<size_t> cl;
-            for (int i = 0; i < n; i++)
-                if (in_b[i]) {
-                    cp.push_back({st.bounce + ioff[i], (const char *)blks[i].src});
-                    cl.push_back(blks[i].src_len);
-                    c->bounce.bytes_in += blks[i].src_len;
-                }
-            par_copy(cp, cl);
-        }
+        if ((rc = st.hs.reserve(c, img_bytes, page_bytes))) return rc;
     }
     // block records; the Open and CRC stages' blocks
     LoadBlk *hl = (LoadBlk *)(h + o_lb);
@@ -2070,16 +2179,7 @@ int load_enqueue(jfsx_ctx *c, int algo, int codec, int n, const jfsx_lblk *blks,
         }
     }
     HIP_OK(hipMemcpyAsync(d + o_lb, h + o_lb, sizeof(LoadBlk) * n, hipMemcpyHostToDevice, s));
-    if (host) {
-        if (all_in && img_bytes) {
-            HIP_OK(hipMemcpyAsync(stage, st.bounce, img_bytes, hipMemcpyHostToDevice, s));
-        } else {
-            for (int i = 0; i < n; i++)
-                if (blks[i].src_len)
-                    HIP_OK(hipMemcpyAsync(stage + ioff[i], in_b[i] ? st.bounce + ioff[i] : (const char *)blks[i].src,
-                                          blks[i].src_len, hipMemcpyHostToDevice, s));
-        }
-    }
+    if (host && (rc = st.hs.upload(s, stage, img_bytes, up_items))) return rc;
     const LoadBlk *dl = (const LoadBlk *)(d + o_lb);
     ZDev *dz = (ZDev *)(d + o_z);
     ZOut *dzo = (ZOut *)(d + o_zo);
@@ -2109,17 +2209,7 @@ int load_enqueue(jfsx_ctx *c, int algo, int codec, int n, const jfsx_lblk *blks,
     HIP_OK(hipGetLastError());
     // 6. results (and, host, the CRC words behind them) in one download; host: every page
     HIP_OK(hipMemcpyAsync(h + st.h_res, d + o_res, down, hipMemcpyDeviceToHost, s));
-    if (host) {
-        const char *pages = stage + img_bytes;
-        if (all_out && page_bytes) {
-            HIP_OK(hipMemcpyAsync(st.bounce, pages, page_bytes, hipMemcpyDeviceToHost, s));
-        } else {
-            for (int i = 0; i < n; i++)
-                if (blks[i].len)
-                    HIP_OK(hipMemcpyAsync(st.out_b[i] ? st.bounce + st.poff[i] : (char *)blks[i].dst,
-                                          pages + st.poff[i], blks[i].len, hipMemcpyDeviceToHost, s));
-        }
-    }
+    if (host) return st.hs.download(s, stage + img_bytes, page_bytes, std::move(down_items));
     return 0;
 }
 
@@ -2130,29 +2220,12 @@ int run_load(jfsx_ctx *c, int algo, int codec, int n, jfsx_lblk *blks, int crc_m
     const bool host = mem == JFSX_MEM_HOST;
     LoadState st;
     rc = load_enqueue(c, algo, codec, n, blks, crc_mode, host, st);
-    // the one wait of the call; after an enqueue error, nothing of it is left in flight
-    const hipError_t se = hipStreamSynchronize(c->stream);
-    for (Workspace *w : {&c->load_aead, &c->load_crc}) {
-        if (!rc && se == hipSuccess && w->timed && w->nt) {
-            hipEvent_t *ev = w == &c->load_aead ? c->load_ev : c->load_ev + 2;
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) add_kernel_ms(c, ms);
-            else (void)hipGetLastError();
-        }
-        w->n = 0;
-        w->nt = 0;
-        w->timed = false;
-        w->crc_back = false;
-    }
-    if (!rc && se != hipSuccess) {
-        note_hip_error(se, __FILE__, __LINE__, "hipStreamSynchronize(load)");
-        rc = JFSX_EIO;
-    }
+    rc = wait_stream(c, rc, "hipStreamSynchronize(load)");  // the one wait of the call
+    settle_stage(c, c->load_aead, c->load_ev[0], c->load_ev[1], !rc);
+    settle_stage(c, c->load_crc, c->load_ev[2], c->load_ev[3], !rc);
     if (!rc) {
         const LoadRes *hr = (const LoadRes *)(c->load_h + st.h_res);
         const char *hw = c->load_h + st.h_res + st.crc_off;
-        std::vector<std::pair<char *, const char *>> cp;
-        std::vector<size_t> cl;
         for (int i = 0; i < n; i++) {
             jfsx_lblk &b = blks[i];
             b.status = hr[i].status;
@@ -2162,15 +2235,9 @@ int run_load(jfsx_ctx *c, int algo, int codec, int n, jfsx_lblk *blks, int crc_m
                 memcpy(b.crc, hw, 4 * nseg_of(b.len));
                 hw += 4 * nseg_of(b.len);
             }
-            if (host && st.out_b[i]) {
-                cp.push_back({(char *)b.dst, st.bounce + st.poff[i]});
-                cl.push_back(b.len);
-                c->bounce.bytes_out += b.len;
-            }
         }
-        par_copy(cp, cl);
+        st.hs.copy_out();
     }
-    if (st.bounce) bounce_put(c, st.bounce, st.bcap);
     if (rc) return rc;
     // jfsx_ctx_metrics: what the separate calls would have counted
     std::lock_guard<std::mutex> g(c->stat_mu);
@@ -2249,16 +2316,13 @@ struct StoreState {
     bool plain = false;      // jfsx_store_objects with JFSX_CODEC_NONE: no compressor, the Seal reads the pages
     size_t obj_extra = 0;    // jfsx_store_objects: bytes of an object's slot beyond its image (frame, alignment)
     int page_mode = 0;       // JFSX_CRC_NONE / GEN / VERIFY of the pages
-    char *bounce = nullptr;  // pinned staging of the call's pageable pages (up) and images (down)
-    size_t bcap = 0;
+    HostStage hs;            // host: the pages up, the images (objects) down
     CompSetup cs;
     std::vector<uint64_t> cap;   // the codec's bound of every page length: the compressor's capacity
-    std::vector<size_t> poff;    // host: page i at store_stage + poff[i], and at bounce + poff[i]
+    std::vector<size_t> poff;    // host: page i at store_stage + poff[i]
     std::vector<size_t> zoff;    // the compressor's output slot of block i at slots + zoff[i]
-    std::vector<size_t> ooff;    // host, phase B: image i at store_img + ooff[i], and at bounce + ooff[i]
+    std::vector<size_t> ooff;    // host, phase B: image i at store_img + ooff[i], and there in the bounce buffer
     char *slots = nullptr;       // null: the compressor writes to the callers' dst (device, no cipher)
-    std::vector<char> in_b, out_b;  // host: page i goes up / image i comes down through the bounce buffer
-    bool all_in = false, all_out = false;
     size_t page_bytes = 0;
     std::vector<jfsx_blk> pb;    // the page CRC stage's blocks
     std::vector<jfsx_blk> sb;    // phase B: the Seal's / the image CRC stage's blocks, OK blocks only
@@ -2277,8 +2341,6 @@ int store_phase_a(jfsx_ctx *c, int n, const jfsx_sblk *blks, StoreState &st) {
     st.cap.assign(n, 0);
     st.poff.assign(n, 0);
     st.zoff.assign(n, 0);
-    st.in_b.assign(n, 0);
-    st.out_b.assign(n, 0);
     size_t page_bytes = 0, slot_bytes = 0, out_max = 0;
     for (int i = 0; i < n; i++) {
         st.cap[i] = st.plain ? blks[i].len : st.zstd ? zstd_bound(blks[i].len) : lz4_bound(blks[i].len);
@@ -2310,35 +2372,18 @@ int store_phase_a(jfsx_ctx *c, int n, const jfsx_sblk *blks, StoreState &st) {
     if (stage_need && (rc = ensure_dev(c, &c->store_stage, &c->store_scap, stage_need))) return rc;
     char *d = c->store_d, *h = c->store_h, *stage = c->store_stage;
     st.slots = use_slots ? stage + (host ? page_bytes : 0) : nullptr;
-    // host: which pages and images go through the bounce pool (pageable caller
-    // memory).  One buffer serves both directions: the stream has finished the
-    // uploads out of it at wait #1, before phase B downloads into it.
-    bool any_in = false, any_out = false;
-    st.all_in = st.all_out = host;
+    // host: the pages up.  Every destination is classified here, by its
+    // capacity, because the buffer of both directions is taken now; which
+    // images come down, and how long they are, only phase B knows
+    std::vector<StageItem> up_items;
     if (host) {
+        st.hs.resize(n, n);
         for (int i = 0; i < n; i++) {
-            if (blks[i].len) {
-                st.in_b[i] = !host_pinned(blks[i].src, blks[i].len);
-                st.all_in = st.all_in && st.in_b[i];
-                any_in = any_in || st.in_b[i];
-            }
-            st.out_b[i] = !host_pinned(blks[i].dst, st.cap[i] + st.obj_extra);
-            st.all_out = st.all_out && st.out_b[i];
-            any_out = any_out || st.out_b[i];
+            if (blks[i].len) HostStage::mark(st.hs.in, i, blks[i].src, blks[i].len);
+            HostStage::mark(st.hs.out, i, blks[i].dst, st.cap[i] + st.obj_extra);
+            up_items.push_back({(void *)blks[i].src, stage + st.poff[i], st.poff[i], blks[i].len, (size_t)i});
         }
-        const size_t need = std::max(any_in ? page_bytes : 0, any_out ? out_max : 0);
-        if (need) {
-            if (!(st.bounce = bounce_get(c, need, &st.bcap))) return JFSX_ENOMEM;
-            std::vector<std::pair<char *, const char *>> cp;
-            std::vector<size_t> cl;
-            for (int i = 0; i < n; i++)
-                if (st.in_b[i]) {
-                    cp.push_back({st.bounce + st.poff[i], (const char *)blks[i].src});
-                    cl.push_back(blks[i].len);
-                    c->bounce.bytes_in += blks[i].len;
-                }
-            par_copy(cp, cl);
-        }
+        if ((rc = st.hs.reserve(c, page_bytes, out_max))) return rc;
     }
     // block records; the page CRC stage's blocks
     StoreBlk *hs = (StoreBlk *)(h + o_sb);
@@ -2360,17 +2405,7 @@ int store_phase_a(jfsx_ctx *c, int n, const jfsx_sblk *blks, StoreState &st) {
     }
     // 1. upload: the records, and every page once
     if (!st.plain) HIP_OK(hipMemcpyAsync(d + o_sb, h + o_sb, sizeof(StoreBlk) * n, hipMemcpyHostToDevice, s));
-    if (host) {
-        if (st.all_in && page_bytes) {
-            HIP_OK(hipMemcpyAsync(stage, st.bounce, page_bytes, hipMemcpyHostToDevice, s));
-        } else {
-            for (int i = 0; i < n; i++)
-                if (blks[i].len)
-                    HIP_OK(hipMemcpyAsync(stage + st.poff[i],
-                                          st.in_b[i] ? st.bounce + st.poff[i] : (const char *)blks[i].src,
-                                          blks[i].len, hipMemcpyHostToDevice, s));
-        }
-    }
+    if (host && (rc = st.hs.upload(s, stage, page_bytes, up_items))) return rc;
     // 2. checksum() of every page, or its verify; the BlkOut[n] stays on the device
     const BlkOut *verified = nullptr;
     if (page_mode) {
@@ -2449,15 +2484,12 @@ int store_phase_b(jfsx_ctx *c, int algo, int n, const jfsx_sblk *blks, StoreStat
         HIP_OK(hipMemcpyAsync(w.h + w.res_off, w.dout, w.down, hipMemcpyDeviceToHost, s));
     }
     if (host && m) {
-        if (st.aead && st.all_out) {
-            HIP_OK(hipMemcpyAsync(st.bounce, c->store_img, out_bytes, hipMemcpyDeviceToHost, s));
-        } else {
-            for (int i : st.okidx) {
-                const char *img = st.aead ? c->store_img + st.ooff[i] : st.slots + st.zoff[i];
-                HIP_OK(hipMemcpyAsync(st.out_b[i] ? st.bounce + st.ooff[i] : (char *)blks[i].dst, img, hr[i].out_len,
-                                      hipMemcpyDeviceToHost, s));
-            }
-        }
+        // the sealed images lie packed in store_img; without a cipher they stay in the compressor's slots
+        std::vector<StageItem> items;
+        for (int i : st.okidx)
+            items.push_back({blks[i].dst, st.aead ? c->store_img + st.ooff[i] : st.slots + st.zoff[i], st.ooff[i],
+                             hr[i].out_len, (size_t)i});
+        return st.hs.download(s, c->store_img, st.aead ? out_bytes : 0, std::move(items));
     }
     return 0;
 }
@@ -2472,38 +2504,18 @@ int run_store(jfsx_ctx *c, int algo, int codec, int n, jfsx_sblk *blks, int crc_
     st.ct = (crc_mode & JFSX_CRC_CT) != 0;
     st.zstd = codec == JFSX_CODEC_ZSTD;
     st.page_mode = crc_mode & 3;
-    // a wait ends a phase; after an enqueue error nothing of the call is left in flight
-    auto wait = [&](const char *what) {
-        const hipError_t se = hipStreamSynchronize(c->stream);
-        if (!rc && se != hipSuccess) {
-            note_hip_error(se, __FILE__, __LINE__, what);
-            rc = JFSX_EIO;
-        }
-    };
-    rc = store_phase_a(c, n, blks, st);
-    wait("hipStreamSynchronize(store, wait #1)");
-    if (!rc) {
-        rc = store_phase_b(c, algo, n, blks, st);
-        wait("hipStreamSynchronize(store, wait #2)");
-    }
+    rc = wait_stream(c, store_phase_a(c, n, blks, st), "hipStreamSynchronize(store, wait #1)");
+    if (!rc) rc = wait_stream(c, store_phase_b(c, algo, n, blks, st), "hipStreamSynchronize(store, wait #2)");
     // the stages' results (tags, ciphertext CRC words, page CRC words) and main-kernel times
     Workspace *ws[3] = {&c->store_crc, &c->store_aead, &c->store_ct};
     jfsx_blk *wb[3] = {st.pb.data(), st.sb.data(), st.sb.data()};
     for (int k = 0; k < 3; k++) {
         Workspace &w = *ws[k];
-        if (!rc && w.n) {
-            rc = finish_aead(c, w, c->store_ev[2 * k], c->store_ev[2 * k + 1], k != 1, wb[k]);
-        } else {
-            w.n = 0;
-            w.nt = 0;
-            w.timed = false;
-            w.crc_back = false;
-        }
+        if (!rc && w.n) rc = finish_aead(c, w, c->store_ev[2 * k], c->store_ev[2 * k + 1], k != 1, wb[k]);
+        else settle_stage(c, w, c->store_ev[2 * k], c->store_ev[2 * k + 1], false);
     }
     if (!rc) {
         const StoreRes *hr = (const StoreRes *)(c->store_h + st.h_res);
-        std::vector<std::pair<char *, const char *>> cp;
-        std::vector<size_t> cl;
         for (int i = 0; i < n; i++) {
             jfsx_sblk &b = blks[i];
             b.status = hr[i].status;
@@ -2534,15 +2546,9 @@ int run_store(jfsx_ctx *c, int algo, int codec, int n, jfsx_sblk *blks, int crc_
                 }
                 cw += nseg_of(b.out_len);
             }
-            if (st.host && st.out_b[st.okidx[k]]) {
-                cp.push_back({(char *)b.dst, st.bounce + st.ooff[st.okidx[k]]});
-                cl.push_back(b.out_len);
-                c->bounce.bytes_out += b.out_len;
-            }
         }
-        par_copy(cp, cl);
+        st.hs.copy_out();
     }
-    if (st.bounce) bounce_put(c, st.bounce, st.bcap);
     if (rc) return rc;
     // jfsx_ctx_metrics: what the separate calls would have counted
     std::lock_guard<std::mutex> g(c->stat_mu);
@@ -4071,10 +4077,8 @@ int check_objects_args(const jfsx_rsa_key *key, int algo, int codec, int n, cons
 }
 
 struct ObjLoadState {
-    char *bounce = nullptr;
-    size_t bcap = 0;
+    HostStage hs;
     std::vector<size_t> poff;
-    std::vector<char> out_b;
     size_t h_res = 0, st_off = 0, crc_off = 0;  // the download in load_h; ObjState[n] and CRC words behind LoadRes[n]
     int zd_waves = 0;
     bool aead = false, crc = false, ct = false, coded = false;
@@ -4092,7 +4096,6 @@ int objects_enqueue(jfsx_ctx *c, const jfsx_rsa_key *key, int algo, int codec, i
     const size_t K = (size_t)kbytes;
     std::vector<size_t> ioff(n);
     st.poff.assign(n, 0);
-    st.out_b.assign(n, 0);
     size_t img_bytes = 0, page_bytes = 0;
     uint64_t crc_words = 0, ct_words = 0, max_len = 0;
     for (int i = 0; i < n; i++) {
@@ -4142,34 +4145,18 @@ int objects_enqueue(jfsx_ctx *c, const jfsx_rsa_key *key, int algo, int codec, i
         if ((rc = ensure_host(&c->rsa_h, &c->rsa_hcap, align256(K * n)))) return rc;
     }
     char *d = c->load_d, *h = c->load_h, *stage = c->load_stage;
-    std::vector<char> in_b(n, 0);
-    bool all_in = host, all_out = host, any_in = false, any_out = false;
+    // host: the stored bytes up and the pages down, as load_enqueue stages them
+    std::vector<StageItem> up_items, down_items;
     if (host) {
+        st.hs.resize(n, n);
         for (int i = 0; i < n; i++) {
-            if (blks[i].src_len) {
-                in_b[i] = !host_pinned(blks[i].src, blks[i].src_len);
-                all_in = all_in && in_b[i];
-                any_in = any_in || in_b[i];
-            }
-            if (blks[i].len) {
-                st.out_b[i] = !host_pinned(blks[i].dst, blks[i].len);
-                all_out = all_out && st.out_b[i];
-                any_out = any_out || st.out_b[i];
-            }
+            const jfsx_oblk &b = blks[i];
+            if (b.src_len) HostStage::mark(st.hs.in, i, b.src, b.src_len);
+            if (b.len) HostStage::mark(st.hs.out, i, b.dst, b.len);
+            up_items.push_back({(void *)b.src, stage + ioff[i], ioff[i], b.src_len, (size_t)i});
+            down_items.push_back({b.dst, stage + img_bytes + st.poff[i], st.poff[i], b.len, (size_t)i});
         }
-        const size_t need = std::max(any_in ? img_bytes : 0, any_out ? page_bytes : 0);
-        if (need) {
-            if (!(st.bounce = bounce_get(c, need, &st.bcap))) return JFSX_ENOMEM;
-            std::vector<std::pair<char *, const char *>> cp;
-            std::vector<size_t> cl;
-            for (int i = 0; i < n; i++)
-                if (in_b[i]) {
-                    cp.push_back({st.bounce + ioff[i], (const char *)blks[i].src});
-                    cl.push_back(blks[i].src_len);
-                    c->bounce.bytes_in += blks[i].src_len;
-                }
-            par_copy(cp, cl);
-        }
+        if ((rc = st.hs.reserve(c, img_bytes, page_bytes))) return rc;
     }
     // block records; the blocks of the image CRC, Open and page CRC stages; the wrapped keys
     LoadBlk *hl = (LoadBlk *)(h + o_lb);
@@ -4237,16 +4224,7 @@ int objects_enqueue(jfsx_ctx *c, const jfsx_rsa_key *key, int algo, int codec, i
     // 1. records, images (host) and wrapped keys up
     HIP_OK(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, s));
     HIP_OK(hipMemsetAsync(d + o_st, 0, sizeof(ObjState) * n, s));
-    if (host) {
-        if (all_in && img_bytes) {
-            HIP_OK(hipMemcpyAsync(stage, st.bounce, img_bytes, hipMemcpyHostToDevice, s));
-        } else {
-            for (int i = 0; i < n; i++)
-                if (blks[i].src_len)
-                    HIP_OK(hipMemcpyAsync(stage + ioff[i], in_b[i] ? st.bounce + ioff[i] : (const char *)blks[i].src,
-                                          blks[i].src_len, hipMemcpyHostToDevice, s));
-        }
-    }
+    if (host && (rc = st.hs.upload(s, stage, img_bytes, up_items))) return rc;
     char *r = c->rsa_d;
     if (aead) HIP_OK(hipMemcpyAsync(r + r_ct, c->rsa_h, K * n, hipMemcpyHostToDevice, s));
     const LoadBlk *dl = (const LoadBlk *)(d + o_lb);
@@ -4297,17 +4275,7 @@ int objects_enqueue(jfsx_ctx *c, const jfsx_rsa_key *key, int algo, int codec, i
     launch_load_wipe(s, n, groups, dl, dres, crc);
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpyAsync(h + st.h_res, d + o_res, down, hipMemcpyDeviceToHost, s));
-    if (host) {
-        const char *pages = stage + img_bytes;
-        if (all_out && page_bytes) {
-            HIP_OK(hipMemcpyAsync(st.bounce, pages, page_bytes, hipMemcpyDeviceToHost, s));
-        } else {
-            for (int i = 0; i < n; i++)
-                if (blks[i].len)
-                    HIP_OK(hipMemcpyAsync(st.out_b[i] ? st.bounce + st.poff[i] : (char *)blks[i].dst,
-                                          pages + st.poff[i], blks[i].len, hipMemcpyDeviceToHost, s));
-        }
-    }
+    if (host) return st.hs.download(s, stage + img_bytes, page_bytes, std::move(down_items));
     return 0;
 }
 
@@ -4317,29 +4285,14 @@ int run_objects(jfsx_ctx *c, const jfsx_rsa_key *key, int algo, int codec, int n
     const bool host = mem == JFSX_MEM_HOST;
     ObjLoadState st;
     int rc = objects_enqueue(c, key, algo, codec, n, blks, crc_mode, host, st);
-    const hipError_t se = hipStreamSynchronize(c->stream);
-    for (Workspace *w : {&c->load_aead, &c->load_crc, &c->obj_ct}) {
-        if (!rc && se == hipSuccess && w->timed && w->nt) {
-            hipEvent_t *ev = w == &c->load_aead ? c->load_ev : w == &c->load_crc ? c->load_ev + 2 : c->obj_ev;
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) add_kernel_ms(c, ms);
-            else (void)hipGetLastError();
-        }
-        w->n = 0;
-        w->nt = 0;
-        w->timed = false;
-        w->crc_back = false;
-    }
-    if (!rc && se != hipSuccess) {
-        note_hip_error(se, __FILE__, __LINE__, "hipStreamSynchronize(load_objects)");
-        rc = JFSX_EIO;
-    }
+    rc = wait_stream(c, rc, "hipStreamSynchronize(load_objects)");
+    settle_stage(c, c->load_aead, c->load_ev[0], c->load_ev[1], !rc);
+    settle_stage(c, c->load_crc, c->load_ev[2], c->load_ev[3], !rc);
+    settle_stage(c, c->obj_ct, c->obj_ev[0], c->obj_ev[1], !rc);
     if (!rc) {
         const LoadRes *hr = (const LoadRes *)(c->load_h + st.h_res);
         const ObjState *hs = (const ObjState *)(c->load_h + st.h_res + st.st_off);
         const char *hw = c->load_h + st.h_res + st.crc_off;
-        std::vector<std::pair<char *, const char *>> cp;
-        std::vector<size_t> cl;
         for (int i = 0; i < n; i++) {
             jfsx_oblk &b = blks[i];
             b.status = hr[i].status;
@@ -4351,15 +4304,9 @@ int run_objects(jfsx_ctx *c, const jfsx_rsa_key *key, int algo, int codec, int n
                 memcpy(b.crc, hw, 4 * nseg_of(b.len));
                 hw += 4 * nseg_of(b.len);
             }
-            if (host && st.out_b[i]) {
-                cp.push_back({(char *)b.dst, st.bounce + st.poff[i]});
-                cl.push_back(b.len);
-                c->bounce.bytes_out += b.len;
-            }
         }
-        par_copy(cp, cl);
+        st.hs.copy_out();
     }
-    if (st.bounce) bounce_put(c, st.bounce, st.bcap);
     if (rc) return rc;
     // jfsx_ctx_metrics: what the separate calls would have counted
     std::lock_guard<std::mutex> g(c->stat_mu);
@@ -4620,15 +4567,12 @@ int sobj_phase_b(jfsx_ctx *c, int algo, int n, const jfsx_soblk *blks, SobjState
         }
     }
     if (host) {
-        if (st.all_out) {
-            HIP_OK(hipMemcpyAsync(st.bounce, c->store_img, out_bytes, hipMemcpyDeviceToHost, s));
-        } else {
-            for (int i : st.okidx) {
-                const size_t at = st.ooff[i] + kObjLead;
-                HIP_OK(hipMemcpyAsync(st.out_b[i] ? st.bounce + at : (char *)blks[i].obj, c->store_img + at,
-                                      obj_frame(so.kbytes) + so.res[i].out_len, hipMemcpyDeviceToHost, s));
-            }
+        std::vector<StageItem> items;
+        for (int i : st.okidx) {
+            const size_t at = st.ooff[i] + kObjLead;
+            items.push_back({blks[i].obj, c->store_img + at, at, obj_frame(so.kbytes) + so.res[i].out_len, (size_t)i});
         }
+        if ((rc = st.hs.download(s, c->store_img, out_bytes, std::move(items)))) return rc;
     }
     return tail ? (*tail)(so) : 0;
 }
@@ -4646,13 +4590,6 @@ int run_store_objects(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t e, int algo
     st.plain = codec == JFSX_CODEC_NONE;
     st.page_mode = crc_mode & 3;
     st.obj_extra = kObjLead + obj_frame(key->kbytes) + 15;
-    auto wait = [&](const char *what) {
-        const hipError_t se = hipStreamSynchronize(c->stream);
-        if (!rc && se != hipSuccess) {
-            note_hip_error(se, __FILE__, __LINE__, what);
-            rc = JFSX_EIO;
-        }
-    };
     // the blocks as store_phase_a takes them; dst is looked at (pinned or not), never written
     std::vector<jfsx_sblk> sh(n);
     for (int i = 0; i < n; i++) {
@@ -4667,7 +4604,7 @@ int run_store_objects(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t e, int algo
     const bool verify = st.page_mode == JFSX_CRC_VERIFY, wait1 = !st.plain || verify;
     rc = sobj_wrap(c, key, e, n, blks, so);
     if (!rc) rc = store_phase_a(c, n, sh.data(), st);
-    if (wait1 || rc) wait("hipStreamSynchronize(store_objects, wait #1)");
+    if (wait1 || rc) rc = wait_stream(c, rc, "hipStreamSynchronize(store_objects, wait #1)");
     bool crc_done = false;  // the page CRC stage's results are in its mirror
     if (!rc) {
         so.res.assign(n, StoreRes{});
@@ -4690,7 +4627,7 @@ int run_store_objects(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t e, int algo
     }
     if (!rc) {
         rc = sobj_phase_b(c, algo, n, blks, so, tail);
-        wait("hipStreamSynchronize(store_objects, wait #2)");
+        rc = wait_stream(c, rc, "hipStreamSynchronize(store_objects, wait #2)");
     }
     // the page CRC stage (GEN with a codec: the CRC words to the callers' host
     // arrays) and the Seal (JFSX_CODEC_NONE with GEN, host: the words of its fused pass)
@@ -4699,27 +4636,15 @@ int run_store_objects(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t e, int algo
         crc_done = true;
     }
     Workspace &w = c->store_aead;
-    if (!rc && w.n) {
-        if (w.timed && w.nt) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, c->store_ev[2], c->store_ev[3]) == hipSuccess) add_kernel_ms(c, ms);
-            else (void)hipGetLastError();
-        }
-        if (so.seal_pages && st.host) {
-            const char *hw = w.h + w.crc_off;
-            for (size_t k = 0; k < st.okidx.size(); k++) {
-                jfsx_soblk &b = blks[st.okidx[k]];
-                memcpy(b.crc, hw + 4 * so.seg_word[k], 4 * nseg_of(b.len));
-            }
+    if (!rc && w.n && so.seal_pages && st.host) {
+        const char *hw = w.h + w.crc_off;
+        for (size_t k = 0; k < st.okidx.size(); k++) {
+            jfsx_soblk &b = blks[st.okidx[k]];
+            memcpy(b.crc, hw + 4 * so.seg_word[k], 4 * nseg_of(b.len));
         }
     }
-    for (Workspace *x : {&c->store_crc, &c->store_aead}) {
-        if (x == &c->store_crc && crc_done && !rc) continue;
-        x->n = 0;
-        x->nt = 0;
-        x->timed = false;
-        x->crc_back = false;
-    }
+    settle_stage(c, w, c->store_ev[2], c->store_ev[3], !rc && w.n);
+    if (!(crc_done && !rc)) settle_stage(c, c->store_crc, c->store_ev[0], c->store_ev[1], false);
     if (c->rsa_h) memset(c->rsa_h, 0, std::min(c->rsa_hcap, so.msg_bytes));  // the pinned copy of the data keys
     if (!rc) {
         const SobjRes *hr = (const SobjRes *)(c->store_h + so.h_sres);
@@ -4741,15 +4666,9 @@ int run_store_objects(jfsx_ctx *c, const jfsx_rsa_key *key, uint32_t e, int algo
             b.out_len = hr[k].out_len;
             b.img_len = hr[k].img_len;
             b.obj_crc = hr[k].obj_crc;
-            if (st.host && st.out_b[i]) {
-                cp.push_back({(char *)b.obj, st.bounce + st.ooff[i] + kObjLead});
-                cl.push_back(b.out_len);
-                c->bounce.bytes_out += b.out_len;
-            }
         }
-        par_copy(cp, cl);
+        st.hs.copy_out();
     }
-    if (st.bounce) bounce_put(c, st.bounce, st.bcap);
     if (rc) return rc;
     // jfsx_ctx_metrics: what the separate calls would have counted
     std::lock_guard<std::mutex> g(c->stat_mu);
@@ -4907,102 +4826,51 @@ int gather_enqueue(jfsx_ctx *c, const uint8_t *const *sp, int n_dst, uint8_t *co
     return 0;
 }
 
-// Under c->mu.  Host memory is staged as the other calls stage it
-// (objects_enqueue): gat_stage holds the sources and, behind them, the
-// destinations; pageable buffers go through one pinned bounce buffer, packed,
-// in one copy up and one copy down when all of a direction are pageable;
-// engine-pinned buffers are copied where they lie.
+// Under c->mu.  Host memory: gat_stage holds the sources and, behind them, the
+// destinations; an empty buffer is not classified.
 int run_gather(jfsx_ctx *c, int n_src, const jfsx_gsrc *src, int n_dst, const jfsx_gdst *dst, const uint64_t *dlen,
                const GatherRun *runs, const jfsx_piece *pieces, bool host) {
     hipStream_t s = c->stream;
     std::vector<const uint8_t *> sp(n_src, nullptr);
     std::vector<uint8_t *> dp(n_dst, nullptr);
-    std::vector<size_t> soff(n_src), doff(n_dst);
-    std::vector<char> in_b(n_src, 0), out_b(n_dst, 0);
-    size_t src_bytes = 0, dst_bytes = 0, bcap = 0;
-    char *bounce = nullptr;
-    bool all_in = host, all_out = host, any_in = false, any_out = false;
+    HostStage hs;
+    std::vector<StageItem> up_items, down_items;
+    size_t src_bytes = 0, dst_bytes = 0;
     int rc = 0;
     if (host) {
-        for (int i = 0; i < n_src; i++) soff[i] = src_bytes, src_bytes += align256(src[i].len);
-        for (int j = 0; j < n_dst; j++) doff[j] = dst_bytes, dst_bytes += align256(dst[j].len);
+        for (int i = 0; i < n_src; i++) src_bytes += align256(src[i].len);
+        for (int j = 0; j < n_dst; j++) dst_bytes += align256(dst[j].len);
         if ((rc = ensure_dev(c, &c->gat_stage, &c->gat_scap, src_bytes + dst_bytes))) return rc;
-        for (int i = 0; i < n_src; i++) {
-            sp[i] = (const uint8_t *)c->gat_stage + soff[i];
-            if (!src[i].len) continue;
-            in_b[i] = !host_pinned(src[i].data, src[i].len);
-            all_in = all_in && in_b[i];
-            any_in = any_in || in_b[i];
+        hs.resize(n_src, n_dst);
+        size_t off = 0;
+        for (int i = 0; i < n_src; off += align256(src[i].len), i++) {
+            sp[i] = (const uint8_t *)c->gat_stage + off;
+            if (src[i].len) HostStage::mark(hs.in, i, src[i].data, src[i].len);
+            up_items.push_back({(void *)src[i].data, c->gat_stage + off, off, src[i].len, (size_t)i});
         }
-        for (int j = 0; j < n_dst; j++) {
-            dp[j] = (uint8_t *)c->gat_stage + src_bytes + doff[j];
-            if (!dst[j].len) continue;
-            out_b[j] = !host_pinned(dst[j].data, dst[j].len);
-            all_out = all_out && out_b[j];
-            any_out = any_out || out_b[j];
+        off = 0;
+        for (int j = 0; j < n_dst; off += align256(dst[j].len), j++) {
+            dp[j] = (uint8_t *)c->gat_stage + src_bytes + off;
+            if (dst[j].len) HostStage::mark(hs.out, j, dst[j].data, dst[j].len);
+            down_items.push_back({dst[j].data, (char *)dp[j], off, dst[j].len, (size_t)j});
         }
-        const size_t need = std::max(any_in ? src_bytes : 0, any_out ? dst_bytes : 0);
-        if (need && !(bounce = bounce_get(c, need, &bcap))) return JFSX_ENOMEM;
-        std::vector<std::pair<char *, const char *>> cp;
-        std::vector<size_t> cl;
-        for (int i = 0; i < n_src; i++)
-            if (in_b[i]) {
-                cp.push_back({bounce + soff[i], (const char *)src[i].data});
-                cl.push_back(src[i].len);
-                c->bounce.bytes_in += src[i].len;
-            }
-        par_copy(cp, cl);
+        if ((rc = hs.reserve(c, src_bytes, dst_bytes))) return rc;
+    } else {
+        for (int i = 0; i < n_src; i++) sp[i] = (const uint8_t *)src[i].data;
+        for (int j = 0; j < n_dst; j++) dp[j] = (uint8_t *)dst[j].data;
     }
     // what is enqueued; the stream is waited for below whatever happens, so a failure does not return at once
     const bool timed = c->timing;
     bool launched = false;
     const auto enqueue = [&]() {
-        if (host && all_in && src_bytes) {
-            HIP_OK(hipMemcpyAsync(c->gat_stage, bounce, src_bytes, hipMemcpyHostToDevice, s));
-        } else if (host) {
-            for (int i = 0; i < n_src; i++)
-                if (src[i].len)
-                    HIP_OK(hipMemcpyAsync((void *)sp[i], in_b[i] ? bounce + soff[i] : (const char *)src[i].data,
-                                          src[i].len, hipMemcpyHostToDevice, s));
-        } else {
-            for (int i = 0; i < n_src; i++) sp[i] = (const uint8_t *)src[i].data;
-            for (int j = 0; j < n_dst; j++) dp[j] = (uint8_t *)dst[j].data;
-        }
-        const int r = gather_enqueue(c, sp.data(), n_dst, dp.data(), dlen, runs, pieces, timed, &launched);
-        if (r) return r;
-        if (host && all_out && dst_bytes) {
-            HIP_OK(hipMemcpyAsync(bounce, c->gat_stage + src_bytes, dst_bytes, hipMemcpyDeviceToHost, s));
-        } else if (host) {
-            for (int j = 0; j < n_dst; j++)
-                if (dst[j].len)
-                    HIP_OK(hipMemcpyAsync(out_b[j] ? bounce + doff[j] : (char *)dst[j].data, dp[j], dst[j].len,
-                                          hipMemcpyDeviceToHost, s));
-        }
-        return 0;
+        int r;
+        if (host && (r = hs.upload(s, c->gat_stage, src_bytes, up_items))) return r;
+        if ((r = gather_enqueue(c, sp.data(), n_dst, dp.data(), dlen, runs, pieces, timed, &launched))) return r;
+        return host ? hs.download(s, c->gat_stage + src_bytes, dst_bytes, std::move(down_items)) : 0;
     };
-    rc = enqueue();
-    const hipError_t se = hipStreamSynchronize(s);
-    if (!rc && se != hipSuccess) {
-        note_hip_error(se, __FILE__, __LINE__, "hipStreamSynchronize(gather)");
-        rc = JFSX_EIO;
-    }
-    if (!rc && timed && launched) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, c->ev_k0[0], c->ev_k1[0]) == hipSuccess) add_kernel_ms(c, ms);
-        else (void)hipGetLastError();
-    }
-    if (!rc && host) {
-        std::vector<std::pair<char *, const char *>> cp;
-        std::vector<size_t> cl;
-        for (int j = 0; j < n_dst; j++)
-            if (out_b[j]) {
-                cp.push_back({(char *)dst[j].data, bounce + doff[j]});
-                cl.push_back(dst[j].len);
-                c->bounce.bytes_out += dst[j].len;
-            }
-        par_copy(cp, cl);
-    }
-    if (bounce) bounce_put(c, bounce, bcap);
+    rc = wait_stream(c, enqueue(), "hipStreamSynchronize(gather)");
+    if (!rc && timed && launched) add_elapsed_ms(c, c->ev_k0[0], c->ev_k1[0]);
+    if (!rc) hs.copy_out();
     return rc;
 }
 
@@ -5451,39 +5319,27 @@ int run_open_range(jfsx_ctx *c, int algo, int n, jfsx_rblk *blks, int crc_mode, 
     cplan.dispatch((Task *)(h + o_ctask));
 
     // host: the blocks' C into the staging
+    // through rng_h, not the pool; every window comes down through it (below)
     char *bounce = nullptr;
-    std::vector<char> in_b(n, 0);
-    bool all_in = host, any_in = false;
+    HostStage hs;
+    std::vector<StageItem> up_items;
     if (host) {
+        hs.resize(n, 0);
         for (int i = 0; i < n; i++) {
-            if (!lens[i]) continue;
-            in_b[i] = !host_pinned(blks[i].src, lens[i]);
-            all_in = all_in && in_b[i];
-            any_in = any_in || in_b[i];
+            if (lens[i]) HostStage::mark(hs.in, i, blks[i].src, lens[i]);
+            up_items.push_back({(void *)blks[i].src, st_src + soff[i], soff[i], (size_t)lens[i], (size_t)i});
         }
-        const size_t need = std::max(any_in ? src_bytes : 0, out_bytes);
+        const size_t need = std::max(hs.need(src_bytes, 0), out_bytes);
         if (need && (rc = ensure_host(&c->rng_h, &c->rng_hcap, need))) return rc;
-        bounce = c->rng_h;
-        std::vector<std::pair<char *, const char *>> cp;
-        std::vector<size_t> cl;
-        for (int i = 0; i < n; i++)
-            if (in_b[i]) {
-                cp.push_back({bounce + soff[i], (const char *)blks[i].src});
-                cl.push_back(lens[i]);
-            }
-        par_copy(cp, cl);
+        hs.lend(bounce = c->rng_h);
     }
     const BlkDev *db = (const BlkDev *)(d + o_blk);
     uint32_t *dpart = (uint32_t *)(d + o_part), *dpexp = (uint32_t *)(d + o_pexp);
     const bool timed = c->timing && (nmt || nat);
     const auto chain = [&]() {
-        if (host && all_in && src_bytes) {
-            HIP_OK(hipMemcpyAsync(st_src, bounce, src_bytes, hipMemcpyHostToDevice, s));
-        } else if (host) {
-            for (int i = 0; i < n; i++)
-                if (lens[i])
-                    HIP_OK(hipMemcpyAsync(st_src + soff[i], in_b[i] ? bounce + soff[i] : (const char *)blks[i].src,
-                                          lens[i], hipMemcpyHostToDevice, s));
+        if (host) {
+            const int r = hs.upload(s, st_src, src_bytes, up_items);
+            if (r) return r;
         }
         HIP_OK(hipMemcpyAsync(d, h, h_bytes, hipMemcpyHostToDevice, s));
         launch_begin();
@@ -5516,22 +5372,9 @@ int run_open_range(jfsx_ctx *c, int algo, int n, jfsx_rblk *blks, int crc_mode, 
         HIP_OK(hipMemcpyAsync(h, d + o_out, down, hipMemcpyDeviceToHost, s));
         return 0;
     };
-    // the stream is waited for whatever the enqueue returned, so a failure leaves nothing in flight
-    const auto settle = [&](int r, const char *what) {
-        const hipError_t se = hipStreamSynchronize(s);
-        if (!r && se != hipSuccess) {
-            note_hip_error(se, __FILE__, __LINE__, what);
-            r = JFSX_EIO;
-        }
-        return r;
-    };
-    rc = settle(chain(), "hipStreamSynchronize(open_range)");
-    if (!rc && timed) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, c->ev_k0[0], c->ev_k1[0]) == hipSuccess) add_kernel_ms(c, ms);
-        else (void)hipGetLastError();
-    }
+    rc = wait_stream(c, chain(), "hipStreamSynchronize(open_range)");
     if (rc) return rc;
+    if (timed) add_elapsed_ms(c, c->ev_k0[0], c->ev_k1[0]);
     // the windows of the blocks that verified, out of the staging
     const BlkOut *ho = (const BlkOut *)h;
     std::vector<const uint8_t *> sp(n, nullptr);
@@ -5570,7 +5413,7 @@ int run_open_range(jfsx_ctx *c, int algo, int n, jfsx_rblk *blks, int crc_mode, 
         }
         return 0;
     };
-    rc = settle(place(), "hipStreamSynchronize(open_range windows)");
+    rc = wait_stream(c, place(), "hipStreamSynchronize(open_range windows)");
     if (!rc) {
         if (host) {
             std::vector<std::pair<char *, const char *>> cp;
